@@ -8,6 +8,11 @@ finalize) = primary + secondary extension rays (ENOUGH_BOUNCES = S_BOUNCED ends 
 after the second vertex, pathtracer.h:33,211), plus, for N > 1, the pack of the owned rows and their
 gather to rank 0 (one rank keeps the finished frame in the core's frame buffer).
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the result
+line; `--dump-outputs DIR` also writes what the last timed step computed (the finished frame, its ray
+counts) as DIR/<name>.npy.  Everything else below (config 4 and the other configurations, the roofline
+launches, the CPU baseline) is measured after the timed steps with `--full` only.
+
 Multi-GPU, two measurements per run:
   value (weak scaling): with N ranks the frame is 1920 x (1080 N) pixels of the same 16:9 view,
     dealt in 8-row bands round-robin, so each GPU traces a 1080p frame's worth of paths per step;
@@ -177,16 +182,37 @@ def timed_frames(core, sc, gather, steps, warmup, world, dev, per_frame=None):
         dist.all_reduce(tot)
         dist.barrier()
     torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        last = step()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
-    return float(el.item()), [int(x) for x in tot.tolist()], counts
+    return float(el.item()), [int(x) for x in tot.tolist()], counts, last
+
+
+DUMP_BUDGET = 64 * 1000 * 1000     # bytes of all --dump-outputs arrays together
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy (float32; integers as float64).  Arrays that
+    together exceed DUMP_BUDGET are cut to an equal share of it each: a fixed (seed 0) sample of their
+    elements, in index order, so that two runs with the same arguments store the same elements."""
+    out = pathlib.Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET:
+        share = DUMP_BUDGET // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrays[k] = a.reshape(-1)[keep]
+    for k, a in arrays.items():
+        np.save(out / f"{k}.npy", a)
 
 
 def config4(args, rank, world, local, dev):
@@ -204,7 +230,7 @@ def config4(args, rank, world, local, dev):
     core.set_tile_bands(rank, world, BAND)
     g = TileGather(rank, world, W4, H4, dev)
     assert core.tile_rows() == g.rows
-    el, tot, _ = timed_frames(core, sc, g, args.config4_steps, args.warmup, world, dev)
+    el, tot, _, _ = timed_frames(core, sc, g, args.config4_steps, args.warmup, world, dev)
     core.close()
     return {"workload": f"config4: room {sc.tri_count} tris (config-3 scene, maxPathLength 4, 2 area lights), "
                         f"{W4}x{H4} 1 spp, frame split across {world} GPU(s) in {BAND}-row bands, RCCL gather of the "
@@ -517,6 +543,12 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--setting", action="append", default=[], help="name=value core setting before loading (A/B runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline kernels, config2_restart, configs 3, 4, 4 in-core "
+                         "and 5 and the CPU baseline (the --no-* switches choose among them); without it: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0): the finished frame and its "
+                         "ray counts")
     args = ap.parse_args()
 
     # provenance: the library must be built from the checked-out sources (lh2_version() "srchash=")
@@ -547,7 +579,7 @@ def main():
     build_s = time.perf_counter() - t0
     gather = TileGather(rank, world, W, H, dev)
     assert core.tile_rows() == gather.rows
-    elapsed, tot, counts = timed_frames(core, sc, gather, args.steps, args.warmup, world, dev)
+    elapsed, tot, counts, last = timed_frames(core, sc, gather, args.steps, args.warmup, world, dev)
     st = core.stats()
     rays_total = tot[0]
     value = rays_total * args.steps / elapsed / 1e6
@@ -555,12 +587,20 @@ def main():
 
     out = None
     if rank == 0:
-        roof, prim, det, model_gbs = roofline_of(core, sc, W, H, dev, args.kernel_iters)
-        # the per-ray byte model of the kernels timed in a step must fit the step at HBM peak (the packet
-        # kernel fetches each node once per 64 rays, so it is priced by its VALU issue, not this model)
-        step_model_gbs = model_gbs * roof["kernel_ms"] / ms_step
-        assert step_model_gbs <= HBM_PEAK_GBS, ("byte model exceeds HBM peak over the step", step_model_gbs)
-        roof["hbm"]["model_GBs_over_step"] = round(step_model_gbs, 1)
+        if args.dump_outputs:
+            # what the last timed step left its caller: one rank, the finished frame in the core's frame buffer; N ranks,
+            # the accumulator rows gathered to rank 0
+            what = {"frame": core.frame()} if world == 1 else {"accumulator": last.cpu().numpy()}
+            dump_outputs(args.dump_outputs, {**what, "ray_counts": core.ray_counts()})
+        roof = prim = None
+        det = {}
+        if args.full:
+            roof, prim, det, model_gbs = roofline_of(core, sc, W, H, dev, args.kernel_iters)
+            # the per-ray byte model of the kernels timed in a step must fit the step at HBM peak (the packet
+            # kernel fetches each node once per 64 rays, so it is priced by its VALU issue, not this model)
+            step_model_gbs = model_gbs * roof["kernel_ms"] / ms_step
+            assert step_model_gbs <= HBM_PEAK_GBS, ("byte model exceeds HBM peak over the step", step_model_gbs)
+            roof["hbm"]["model_GBs_over_step"] = round(step_model_gbs, 1)
         info = core.scene_info()
         out = {
             "metric": "Mrays/s (primary+secondary) at 1080p 1spp",
@@ -578,11 +618,10 @@ def main():
             "config": {"workload": f"config2: {args.tris} random tris (xorshift32 0x12345678), {W}x{H} frame "
                                    f"({args.width}x{args.height} paths per GPU, {BAND}-row bands), 1 spp, "
                                    f"full wavefront frame (primary + bounce-1 rays); strong scaling of config 4 "
-                                   f"(4K, frame split across the GPUs) in 'config4'",
+                                   f"(4K, frame split across the GPUs) in 'config4' (with --full)",
                        "frame": [W, H], "spp": 1, "tris": args.tris, "parallelism": f"tiles{world}",
                        "frames": "a still camera converging: one Restart, then Converge (new samples every step)"},
-            "roofline": roof,
-            "roofline_primary": prim,
+            **({"roofline": roof, "roofline_primary": prim} if args.full else {}),
             "detail": {"primary_rays": int(counts[0]), "secondary_rays": int(counts[1]),
                        "deep_rays": int(counts[2:16].sum()), "shadow_rays": int(counts[16]), **det,
                        "trace_Mrays_s_frame": round(rays_total / world / ((st.traceTime0 + st.traceTime1) * 1e6), 1)
@@ -593,6 +632,12 @@ def main():
             "build": {"srchash": got, "lh2_version": core.lib.lh2_version().decode()},
         }
     core.close()
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     c4 = None if args.no_config4 else config4(args, rank, world, local, dev)
     c4in = c3 = c5 = c2r = None
     if not args.no_configs:

@@ -58,22 +58,56 @@ def test_oracle_visit_model_fixture(config2_oracle):
     assert abs(vis[:, 1].mean() - fix["mean_tri_tests"]) / fix["mean_tri_tests"] < 0.05
 
 
-@pytest.mark.skipif(not REF_LIB.exists(), reason="reference traversal not built")
-def test_oracle_matches_compiled_reference_on_random_rays():
-    import ctypes as C
-    L = C.CDLL(str(REF_LIB))
-    L.bart_build.restype = C.c_void_p
-    L.bart_build.argtypes = [C.c_void_p, C.c_int]
-    L.bart_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+# What the reference compiled from its sources (oracle/_ref, oracle/Makefile.ref) returned for the inputs the tests
+# below build from fixed seeds, recorded by tools/make_fixtures.py pins: the tests compare with the record, so they need
+# no reference build; where oracle/_ref is built they also run it again and it must return the record.  "<name>_in" is
+# the hash of the inputs a record belongs to.
+PIN_GOLD = GOLD / "reference_pins.npz"
+
+
+def _sha(*arrays):
+    import hashlib
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def _recorded(name, *inputs):
+    g = np.load(PIN_GOLD)
+    assert str(g[name + "_in"]) == _sha(*inputs), f"{name}: the record was made for other inputs"
+    return g[name]
+
+
+def random_rays():
     tris = scene.random_triangles(20000, seed=99)
-    h = L.bart_build(tris.ctypes.data, len(tris))
     rng = np.random.default_rng(5)
     n = 20000
     org = (rng.normal(size=(n, 3)) * 8).astype(np.float32)
     d = (rng.uniform(-3, 3, (n, 3)) - org).astype(np.float32)
     d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
-    out = np.zeros((n, 4), np.float32)
-    L.bart_trace(h, org.ctypes.data, d.ctypes.data, n, out.ctypes.data, None, 4)
+    return tris, org, d
+
+
+def reference_random_ray_t(tris, org, d):
+    """Closest-hit t of RenderCore_Bart BVH2::Traverse (oracle/_ref/libbart_ref.so) per ray."""
+    import ctypes as C
+    L = C.CDLL(str(REF_LIB))
+    L.bart_build.restype = C.c_void_p
+    L.bart_build.argtypes = [C.c_void_p, C.c_int]
+    L.bart_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    h = L.bart_build(tris.ctypes.data, len(tris))
+    out = np.zeros((len(org), 4), np.float32)
+    L.bart_trace(h, org.ctypes.data, d.ctypes.data, len(org), out.ctypes.data, None, 4)
+    return np.ascontiguousarray(out[:, 0])
+
+
+def test_oracle_matches_compiled_reference_on_random_rays():
+    tris, org, d = random_rays()
+    n = len(org)
+    out = _recorded("bart_random_t", tris, org, d)[:, None]
+    if REF_LIB.exists():
+        assert np.array_equal(reference_random_ray_t(tris, org, d).view(np.uint32), out[:, 0].view(np.uint32))
     o = Oracle(threads=4)
     o.set_materials([abi.make_material()])
     o.set_geometry(0, tris)
@@ -121,14 +155,7 @@ def _pins():
     return L
 
 
-@pytest.mark.skipif(not PINS.exists(), reason="reference pins not built (no /root/reference)")
-def test_mat4_inverse_matches_reference():
-    """The instance inverse of UpdateToplevel (orc_mat4_inverse; the core's RenderCore::UpdateToplevel
-    and device TLAS build use the same formula) equals lighthouse2::mat4::Inverted bit for bit
-    (RenderSystem/common_types.h:586-628)."""
-    import ctypes as C
-    from oracle import oracle as orc_mod
-    L = _pins()
+def mat4_inputs():
     rng = np.random.default_rng(21)
     mats = []
     for k in range(400):
@@ -144,22 +171,35 @@ def test_mat4_inverse_matches_reference():
         m[:3, 3] = rng.uniform(-50, 50, 3)
         mats.append(np.ascontiguousarray(m, np.float32))
     mats.append(np.zeros((4, 4), np.float32))                       # singular: identity in both
+    return np.stack(mats)
+
+
+def reference_mat4_inverted(mats):
+    L = _pins()
+    ref = np.zeros((len(mats), 16), np.float32)
+    for m, r in zip(mats, ref):
+        L.pin_mat4_inverted(m.ctypes.data, r.ctypes.data)
+    return ref
+
+
+def test_mat4_inverse_matches_reference():
+    """The instance inverse of UpdateToplevel (orc_mat4_inverse; the core's RenderCore::UpdateToplevel
+    and device TLAS build use the same formula) equals lighthouse2::mat4::Inverted bit for bit
+    (RenderSystem/common_types.h:586-628)."""
+    import ctypes as C
+    from oracle import oracle as orc_mod
+    mats = mat4_inputs()
+    refs = _recorded("mat4_inverted", mats)
+    if PINS.exists():
+        assert np.array_equal(reference_mat4_inverted(mats).view(np.uint32), refs.view(np.uint32))
     lib = orc_mod.lib()
-    for m in mats:
-        ref = np.zeros(16, np.float32)
-        L.pin_mat4_inverted(m.ctypes.data, ref.ctypes.data)
+    for m, ref in zip(mats, refs):
         ours = np.zeros(16, np.float32)
         lib.orc_mat4_inverse(m.ravel().ctypes.data_as(C.POINTER(C.c_float)), ours.ctypes.data_as(C.POINTER(C.c_float)))
         assert np.array_equal(ours.view(np.uint32), ref.view(np.uint32)), m
 
 
-@pytest.mark.skipif(not PINS.exists(), reason="reference pins not built (no /root/reference)")
-def test_half_conversion_matches_reference():
-    """lh2_f2h (include/lh2_detmath.h; the core's SetMaterials and the oracle) equals half_float::half(float)
-    of half2.1.0/half.hpp (round to nearest, HALF_ROUND_STYLE 1), the conversion RenderCore_OptixPrime_B
-    applies to material colours, on every rounding tie, subnormals, overflow and random values."""
-    from oracle import oracle as orc_mod
-    L = _pins()
+def half_inputs():
     rng = np.random.default_rng(22)
     h = np.arange(0, 0x7c00, dtype=np.uint32)                   # every finite positive half
     f16 = h.astype(np.uint16).view(np.float16).astype(np.float32)
@@ -168,32 +208,67 @@ def test_half_conversion_matches_reference():
     x = np.concatenate([f16, up, mid, np.nextafter(mid, np.float32(0)), np.nextafter(mid, np.float32(np.inf)),
                         rng.normal(scale=1, size=20000), rng.normal(scale=1e-5, size=5000), rng.normal(scale=3e4, size=5000),
                         np.float32([65504, 65519.99, 65520, 1e10, np.inf])]).astype(np.float32)
-    x = np.concatenate([x, -x])
+    return np.concatenate([x, -x])
+
+
+def reference_float_to_half(x):
     ref = np.zeros(len(x), np.uint16)
-    L.pin_float_to_half(x.ctypes.data, ref.ctypes.data, len(x))
+    _pins().pin_float_to_half(x.ctypes.data, ref.ctypes.data, len(x))
+    return ref
+
+
+def test_half_conversion_matches_reference():
+    """lh2_f2h (include/lh2_detmath.h; the core's SetMaterials and the oracle) equals half_float::half(float)
+    of half2.1.0/half.hpp (round to nearest, HALF_ROUND_STYLE 1), the conversion RenderCore_OptixPrime_B
+    applies to material colours, on every rounding tie, subnormals, overflow and random values."""
+    from oracle import oracle as orc_mod
+    x = half_inputs()
+    ref = _recorded("float_to_half", x)
+    if PINS.exists():
+        assert np.array_equal(reference_float_to_half(x), ref)
     ours = orc_mod.detmath(7, x)                                    # lh2_h2f(lh2_f2h(x))
     want = ref.view(np.float16).astype(np.float32)
     assert np.array_equal(ours.view(np.uint32), want.view(np.uint32))
 
 
-@pytest.mark.skipif(not PINS.exists(), reason="reference pins not built (no /root/reference)")
-@pytest.mark.parametrize("cam", [
+CAMS = [
     ((0, 0, -12), (0, 0, 1), 40, 16 / 9, 5, 0, 0, (1920, 1080)),       # config 2 (bench)
     ((0, 6, 11), (0, -0.15, -1), 60, 16 / 9, 5, 0, 0, (1920, 1080)),   # config 3 room
     ((0, 60, -80), (0, -0.6, 1), 50, 16 / 9, 5, 0, 0, (1920, 1080)),   # config 5
     ((0.3, 0.2, -12), (0.05, -0.02, 1), 50, 96 / 54, 5, 0.05, 0.05, (96, 54)),
     ((1, 30, 2), (0.01, -1, 0.05), 75, 1.0, 2.5, 0.1, 0.0, (640, 640)),   # looking down: CalculateMatrix's other branch
-])
+]
+
+
+def _cam_direction(d):
+    dn = np.asarray(d, np.float64)
+    return (dn / np.linalg.norm(dn)).astype(np.float32)             # Camera::direction is kept normalised
+
+
+def camera_inputs():
+    """Every CAMS entry as the 12 numbers Camera::GetView takes (position, unit direction, the rest)."""
+    return np.float64([[*np.float32(pos), *_cam_direction(d), fov, aspect, focal, aperture, distortion, px, py]
+                       for pos, d, fov, aspect, focal, aperture, distortion, (px, py) in CAMS])
+
+
+def reference_camera_view(cam):
+    pos, d, fov, aspect, focal, aperture, distortion, (px, py) = cam
+    dn = _cam_direction(d)
+    ref = np.zeros(17, np.float32)
+    _pins().pin_camera_view(np.asarray(pos, np.float32).ctypes.data, dn.ctypes.data, fov, aspect, focal, aperture, distortion,
+                            px, py, ref.ctypes.data)
+    return ref
+
+
+@pytest.mark.parametrize("cam", CAMS)
 def test_camera_view_matches_reference(cam):
     """scene.camera_view (the ViewPyramid every test scene and the bench render with) equals
     Camera::GetView (RenderSystem/camera.cpp:96-117) bit for bit."""
-    L = _pins()
     pos, d, fov, aspect, focal, aperture, distortion, (px, py) = cam
-    dn = np.asarray(d, np.float64)
-    dn = (dn / np.linalg.norm(dn)).astype(np.float32)               # Camera::direction is kept normalised
-    ref = np.zeros(17, np.float32)
-    L.pin_camera_view(np.asarray(pos, np.float32).ctypes.data, dn.ctypes.data, fov, aspect, focal, aperture, distortion,
-                      px, py, ref.ctypes.data)
+    dn = _cam_direction(d)
+    ref = _recorded("camera_view", camera_inputs())[CAMS.index(cam)]
+    if PINS.exists():
+        assert np.array_equal(reference_camera_view(cam).view(np.uint32), ref.view(np.uint32))
     v = scene.camera_view(pos, dn, fov_deg=fov, aspect=aspect, focal=focal, aperture=aperture, distortion=distortion,
                           pixel_height=py)
     ours = np.frombuffer(bytes(v), np.float32)

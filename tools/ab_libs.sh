@@ -15,5 +15,5 @@ for rep in 1 2 3; do for lib in new "$@"; do
   echo "$lib $(tail -1 "$OUT/$lib.log" | cut -c1-160)"
 done; done
 unset LH2_CORE_LIB
-timeout -k 10 200 python3 bench.py --steps 20 --no-cpu-baseline --no-config4 > "$OUT/bench.json" 2> "$OUT/bench.log" || exit 1
+timeout -k 10 200 python3 bench.py --full --steps 20 --no-cpu-baseline --no-config4 > "$OUT/bench.json" 2> "$OUT/bench.log" || exit 1
 python3 -c "import json;d=json.load(open('$OUT/bench.json'));print('bench',d['value'],d['ms_per_step'],d['roofline']['kernel_ms'],d['roofline']['frac'],d['detail']['traceTime0_ms'],d['detail']['traceTime1_ms'],d['detail']['shadeTime_ms'])"

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 for rep in $(seq 1 "${REPS:-2}"); do
   for v in ${VALUES:-1 0}; do
-    timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-config5 --setting "$SETTING=$v" > "$OUT/bench_${v}_$rep.json" 2> "$OUT/bench_${v}_$rep.log"
+    timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-config5 --setting "$SETTING=$v" > "$OUT/bench_${v}_$rep.json" 2> "$OUT/bench_${v}_$rep.log"
     timeout -k 10 200 python3 tools/config4_shares.py --ranks 1,8 --setting "$SETTING=$v" > "$OUT/shares_${v}_$rep.jsonl" 2> "$OUT/shares_${v}_$rep.err"
     python3 - "$OUT/bench_${v}_$rep.json" "$OUT/shares_${v}_$rep.jsonl" "$SETTING=$v" <<'PY'
 import json, sys

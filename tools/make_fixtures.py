@@ -7,6 +7,7 @@
    (oracle/_ref/libbart_ref.so built from /root/reference by oracle/Makefile.ref) on a 64x36
    subsample of config-2 primary rays: pins the oracle's traversal (tests/test_golden.py).
 3. oracle_frames.npz - small oracle frames (accumulator + ray counts) used as regression goldens.
+4. reference_pins.npz - the compiled reference's answers (oracle/_ref) on the seeded inputs of tests/test_golden.py.
 """
 from __future__ import annotations
 
@@ -107,12 +108,31 @@ def oracle_frames():
     print("oracle frames:", list(frames))
 
 
+def pins_fixture():
+    """reference_pins.npz: what the reference build returns for the seeded inputs of tests/test_golden.py (the
+    traversal on random rays, mat4::Inverted, half(float), Camera::GetView), each with the hash of its inputs."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import test_golden as t
+    if not (t.REF_LIB.exists() and t.PINS.exists()):
+        print("reference build absent; skipping pins fixture")
+        return
+    rays, mats, x, cams = t.random_rays(), t.mat4_inputs(), t.half_inputs(), t.camera_inputs()
+    rec = {"bart_random_t": t.reference_random_ray_t(*rays), "bart_random_t_in": t._sha(*rays),
+           "mat4_inverted": t.reference_mat4_inverted(mats), "mat4_inverted_in": t._sha(mats),
+           "float_to_half": t.reference_float_to_half(x), "float_to_half_in": t._sha(x),
+           "camera_view": np.stack([t.reference_camera_view(c) for c in t.CAMS]), "camera_view_in": t._sha(cams)}
+    np.savez_compressed(GOLD / "reference_pins.npz", **rec)
+    print("reference pins:", {k: getattr(v, "shape", v) for k, v in rec.items()})
+
+
 if __name__ == "__main__":
     GOLD.mkdir(parents=True, exist_ok=True)
-    which = sys.argv[1:] or ["visits", "bart", "frames"]
+    which = sys.argv[1:] or ["visits", "bart", "frames", "pins"]
     if "visits" in which:
         visits_fixture()
     if "bart" in which:
         bart_fixture()
     if "frames" in which:
         oracle_frames()
+    if "pins" in which:
+        pins_fixture()

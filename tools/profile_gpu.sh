@@ -13,9 +13,9 @@ OUT="$ROOT/gpurun_out/prof"
 mkdir -p "$OUT"
 STEPS="${STEPS:-20}"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 python3 "$ROOT/bench.py" --steps "$STEPS" > "$OUT/bench.json" 2> "$OUT/bench.log" &&
+timeout -k 10 300 python3 "$ROOT/bench.py" --full --steps "$STEPS" > "$OUT/bench.json" 2> "$OUT/bench.log" &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/stats" -o run -- \
-    python3 "$ROOT/bench.py" --steps "$STEPS" --no-cpu-baseline --no-config4 --no-configs > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.log" &&
+    python3 "$ROOT/bench.py" --full --steps "$STEPS" --no-cpu-baseline --no-config4 --no-configs > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.log" &&
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -f csv -d "$OUT/pmc_fetch" -o run -- \
     python3 "$ROOT/tools/trace_kernel_bench.py" --set bounce --iters 10 > "$OUT/pmc_fetch.log" 2>&1 &&
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -f csv -d "$OUT/pmc_write" -o run -- \

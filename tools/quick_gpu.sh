@@ -13,7 +13,7 @@ if [ "${TESTS:-1}" != "0" ]; then
     timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > "$OUT/gpu_tests.log" 2>&1
 fi
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 python3 "$ROOT/bench.py" --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.log" &&
+timeout -k 10 300 python3 "$ROOT/bench.py" --full --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.log" &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/stats" -o run -- \
-    python3 "$ROOT/bench.py" --steps 10 --no-cpu-baseline > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.log"
+    python3 "$ROOT/bench.py" --full --steps 10 --no-cpu-baseline > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.log"
 echo "quick done"

@@ -16,7 +16,7 @@ if [[ "$STEPS" == *t* ]]; then
   tail -1 "$OUT/gpu_tests.log"
 fi
 if [[ "$STEPS" == *b* ]]; then
-  timeout -k 10 400 python3 bench.py --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.log"
+  timeout -k 10 400 python3 bench.py --full --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.log"
   python3 -c "import json;d=json.load(open('$OUT/bench.json'));print('bench',d['value'],d['ms_per_step'],{k:(d[k] or {}).get('ms_per_frame') for k in ('config2_restart','config3','config4','config4_incore','config5')}, (d['config5'] or {}).get('setup_s'))"
 fi
 if [[ "$STEPS" == *s* ]]; then

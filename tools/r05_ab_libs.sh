@@ -30,7 +30,7 @@ for r in $(seq 1 "$R"); do
     uselib "$lib"
     n="${lib}_$r"
     # C5=1: config 5 too (the instanced loops; ~10 s more per bench)
-    timeout -k 10 300 python3 bench.py --no-cpu-baseline $([ -n "${C5:-}" ] || echo --no-config5) --no-config4 > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.log"
+    timeout -k 10 300 python3 bench.py --full --no-cpu-baseline $([ -n "${C5:-}" ] || echo --no-config5) --no-config4 > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.log"
     timeout -k 10 200 python3 tools/config4_shares.py --ranks 1,8 > "$OUT/shares_$n.jsonl" 2> "$OUT/shares_$n.err"
     python3 - "$OUT/bench_$n.json" "$OUT/shares_$n.jsonl" "$n" <<'PY'
 import json, sys

@@ -16,7 +16,7 @@ fi
 for r in $(seq 1 "$R"); do
   for v in $VALS; do
     n="${v}_$r"
-    timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-config5 --no-config4 --setting "$NAME=$v" > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.log"
+    timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-config5 --no-config4 --setting "$NAME=$v" > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.log"
     timeout -k 10 200 python3 tools/config4_shares.py --ranks 1,8 --setting "$NAME=$v" > "$OUT/shares_$n.jsonl" 2> "$OUT/shares_$n.err"
     python3 - "$OUT/bench_$n.json" "$OUT/shares_$n.jsonl" "$NAME=$n" <<'PY'
 import json, sys

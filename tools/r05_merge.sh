@@ -38,7 +38,7 @@ done
 frames() {   # name, lib
   local name="$1" lib="$2"
   if [ -n "$lib" ]; then export LH2_CORE_LIB="$ROOT/gpuab/$lib/libRenderCore_MI355X.so"; else unset LH2_CORE_LIB; fi
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-config5 --no-config4 > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.log"
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-config5 --no-config4 > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.log"
   timeout -k 10 200 python3 tools/config4_shares.py --ranks 1,8 > "$OUT/shares_$name.jsonl" 2> "$OUT/shares_$name.err"
   unset LH2_CORE_LIB
   python3 - "$OUT/bench_$name.json" "$OUT/shares_$name.jsonl" "$name" <<'PY'

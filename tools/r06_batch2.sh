@@ -15,7 +15,7 @@ fi
 timeout -k 10 180 "$ROOT/tools/valu_rate" > "$OUT/valu_rate.jsonl"
 bash tools/valu_rate_pmc.sh
 cd "$ROOT"
-timeout -k 10 400 python3 bench.py --cpu-seconds 5 > "$OUT/bench.json" 2> "$OUT/bench.log"
+timeout -k 10 400 python3 bench.py --full --cpu-seconds 5 > "$OUT/bench.json" 2> "$OUT/bench.log"
 echo "bench: $(python3 -c "import json; d=json.load(open('$OUT/bench.json')); print(d['value'], d['config3']['ms_per_frame'], d['config4']['ms_per_frame'], d['config5']['ms_per_frame'])")"
 for r in 1 2; do
   for v in on off; do

@@ -14,7 +14,7 @@ if [ -n "${TESTS:-1}" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > "$OUT/gpu_tests.log" 2>&1
   tail -1 "$OUT/gpu_tests.log"
 fi
-timeout -k 10 400 python3 bench.py --cpu-seconds 5 > "$OUT/bench.json" 2> "$OUT/bench.log"
+timeout -k 10 400 python3 bench.py --full --cpu-seconds 5 > "$OUT/bench.json" 2> "$OUT/bench.log"
 echo "bench done"
 for r in 1 2; do
   for v in 3 2; do
