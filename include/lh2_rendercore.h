@@ -32,7 +32,8 @@
      lh2_core_set_tile, lh2_core_set_tile_bands, lh2_core_sync, lh2_core_get_accumulator, lh2_core_get_frame,
      lh2_core_copy_accumulator_rows, lh2_core_copy_frame_async, lh2_core_pack_tile, lh2_core_pack_tile_ordered, lh2_core_tile_rows, lh2_core_stream, lh2_core_ray_counts, lh2_core_trace_closest,
      lh2_core_trace_any, lh2_core_trace_closest_device, lh2_core_generate_eye_rays,
-     lh2_core_scene_info, lh2_core_debug_shadow_rays, lh2_core_debug_bvh4, lh2_core_debug_poison_tlas, lh2_core_get_setting, lh2_set_device, lh2_xorshift_floats, lh2_version.
+     lh2_core_scene_info, lh2_core_debug_shadow_rays, lh2_core_debug_bvh4, lh2_core_debug_poison_tlas, lh2_core_get_setting, lh2_set_device, lh2_xorshift_floats, lh2_version,
+     lh2_core_filter_buffer, lh2_core_filter_times, lh2_core_filter_unit (the denoise mode, setting "filter").
 */
 #ifndef LH2_RENDERCORE_H
 #define LH2_RENDERCORE_H
@@ -100,6 +101,42 @@ int lh2_core_debug_shadow_rays( lh2_core core, float* o4, float* d4, float* p4, 
 int lh2_core_debug_bvh4( lh2_core core, float* f32Nodes, uint32_t* qNodes, int cap, int* n );
 /* test hook: fill both TLAS slots' node regions with `value` (stale memory behind the nodes a TLAS update writes) */
 int lh2_core_debug_poison_tlas( lh2_core core, float value );
+
+/* ---- the denoise mode (setting "filter": SVGF, csrc/lh2_filter.h) ---- */
+/* its buffers of the last filtered frame, copied to the host; every record is 16 B per pixel except MOTION (8 B) and the
+   accumulator planes (2 x 16 B: all direct pixels, then all indirect ones) */
+enum
+{
+	LH2_FILTER_BUF_ACC = 0,        /* float4 x 2 planes */
+	LH2_FILTER_BUF_FEATURES,       /* uint4: albedo 10:11:11, packed normal, hit distance, history | specular << 4 | material << 6 */
+	LH2_FILTER_BUF_WORLDPOS,       /* float4 */
+	LH2_FILTER_BUF_DELTADEPTH,     /* float4 */
+	LH2_FILTER_BUF_MOTION,         /* float2 */
+	LH2_FILTER_BUF_MOMENTS,        /* float4 */
+	LH2_FILTER_BUF_SHADING,        /* prepare's output: direct + indirect, 5:11 fixed point */
+	LH2_FILTER_BUF_PHASE1, LH2_FILTER_BUF_PHASE2,   /* the same format */
+	LH2_FILTER_BUF_PHASE3,         /* the frame: linear radiance */
+	LH2_FILTER_BUF_PREVWORLDPOS, LH2_FILTER_BUF_PREVMOMENTS,
+	LH2_FILTER_BUF_COUNT
+};
+int lh2_core_filter_buffer( lh2_core core, int which, void* out );
+int lh2_core_filter_times( lh2_core core, float* ms4 );   /* the last filtered frame: prepare and the three passes (ms) */
+/* one kernel of the chain on host arrays of any w x h (as lh2_core_trace_closest runs the traversal on host rays): stage 0
+   prepare (reads acc, features, worldPos, prevWorldPos, deltaDepth, prevMoments; writes out = shading, motion, moments and
+   features.w); stage 1 .. 3 one a-trous pass (reads features, worldPos, prevWorldPos, deltaDepth, motion, moments, in, and for
+   stage 1 prev = the previous frame's stage-1 output; writes out).  Arrays a stage does not use may be null */
+typedef struct
+{
+	int stage, w, h;
+	int camStationary, historyValid;
+	int lds;                       /* a-trous taps from an LDS tile (1) or through the caches (0) */
+	float scale, clampDirect, clampIndirect;
+	lh2_ViewPyramid prevView, view;   /* prepare: the previous frame's view and this frame's */
+	const float* acc; uint32_t* features; const float* worldPos; const float* prevWorldPos; const float* deltaDepth;
+	float* motion; float* moments; const float* prevMoments;
+	const float* in; const float* prev; float* out;
+} lh2_FilterUnit;
+int lh2_core_filter_unit( lh2_core core, const lh2_FilterUnit* unit );
 
 /* host utility: n successive RandomFloat() values of Marsaglia xorshift32 (platform/system.cpp:44-46) */
 int lh2_xorshift_floats( uint32_t seed, float* out, uint64_t n );

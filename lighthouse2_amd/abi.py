@@ -76,6 +76,15 @@ class ViewPyramid(C.Structure):
                 ("distortion", C.c_float)]
 
 
+class FilterUnit(C.Structure):
+    """lh2_FilterUnit (include/lh2_rendercore.h): one kernel of the denoise chain on host arrays."""
+    _fields_ = [("stage", C.c_int), ("w", C.c_int), ("h", C.c_int), ("camStationary", C.c_int), ("historyValid", C.c_int),
+                ("lds", C.c_int), ("scale", C.c_float), ("clampDirect", C.c_float), ("clampIndirect", C.c_float),
+                ("prevView", ViewPyramid), ("view", ViewPyramid), ("acc", C.c_void_p), ("features", C.c_void_p), ("worldPos", C.c_void_p),
+                ("prevWorldPos", C.c_void_p), ("deltaDepth", C.c_void_p), ("motion", C.c_void_p), ("moments", C.c_void_p),
+                ("prevMoments", C.c_void_p), ("in_", C.c_void_p), ("prev", C.c_void_p), ("out", C.c_void_p)]
+
+
 class CoreStats(C.Structure):
     _fields_ = [("deviceName", C.c_char_p), ("SMcount", C.c_uint32), ("ccMajor", C.c_uint32),
                 ("ccMinor", C.c_uint32), ("VRAM", C.c_uint32), ("argb32TexelCount", C.c_uint32),

@@ -83,6 +83,9 @@ def load_library(path: str | os.PathLike | None = None) -> C.CDLL:
         "lh2_core_debug_shadow_rays": [_P, _F, _F, _F, C.c_int, C.POINTER(C.c_int)],
         "lh2_core_debug_bvh4": [_P, _F, C.c_void_p, C.c_int, C.POINTER(C.c_int)],
         "lh2_core_debug_poison_tlas": [_P, C.c_float],
+        "lh2_core_filter_buffer": [_P, C.c_int, _P],
+        "lh2_core_filter_times": [_P, _F],
+        "lh2_core_filter_unit": [_P, C.POINTER(abi.FilterUnit)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -315,6 +318,62 @@ class RenderCore:
     def debug_poison_tlas(self, value: float) -> None:
         """Test hook: fill both TLAS slots' node regions with `value` (stale memory behind a TLAS update's nodes)."""
         self._chk(self.lib.lh2_core_debug_poison_tlas(self.h, float(value)))
+
+    # --- the denoise mode (setting "filter") -------------------------------------------
+    # lh2_core_filter_buffer selectors (LH2_FILTER_BUF_*): name -> (index, dtype, words per pixel)
+    FILTER_BUFFERS = {
+        "acc": (0, np.float32, 8), "features": (1, np.uint32, 4), "worldPos": (2, np.float32, 4),
+        "deltaDepth": (3, np.float32, 4), "motion": (4, np.float32, 2), "moments": (5, np.float32, 4),
+        "shading": (6, np.uint32, 4), "phase1": (7, np.uint32, 4), "phase2": (8, np.uint32, 4), "phase3": (9, np.float32, 4),
+        "prevWorldPos": (10, np.float32, 4), "prevMoments": (11, np.float32, 4),
+    }
+
+    def filter_buffer(self, name: str) -> np.ndarray:
+        """A buffer of the last filtered frame, (h, w, words); "acc": (2, h, w, 4), the direct and indirect planes.
+        The packed ones (features, shading, phase1, phase2) come as uint32 words."""
+        idx, dtype, words = self.FILTER_BUFFERS[name]
+        out = np.zeros((2, self.h_, self.w, 4) if name == "acc" else (self.h_, self.w, words), dtype)
+        self._chk(self.lib.lh2_core_filter_buffer(self.h, idx, out.ctypes.data_as(_P)))
+        return out
+
+    def filter_times(self) -> np.ndarray:
+        """Kernel times of the last filtered frame in ms: prepare and the three a-trous passes."""
+        out = np.zeros(4, np.float32)
+        self._chk(self.lib.lh2_core_filter_times(self.h, _fp(out)))
+        return out
+
+    def filter_unit(self, stage: int, *, features, worldPos, prevWorldPos, deltaDepth, prev_view: abi.ViewPyramid | None = None,
+                    view: abi.ViewPyramid | None = None,
+                    acc=None, prevMoments=None, motion=None, moments=None, in_=None, prev=None, cam_stationary: bool = True,
+                    history_valid: bool = True, lds: bool = True, scale: float = 1.0, clamp_direct: float = 2.5,
+                    clamp_indirect: float = 15.0) -> dict:
+        """Run prepare (stage 0) or one a-trous pass (stage 1..3) on host arrays of shape (h, w, words).
+        Stage 0 returns shading, motion, moments and the updated features; stages 1..3 return out (packed uint32
+        words for stages 1 and 2, float32 radiance for stage 3)."""
+        features = np.ascontiguousarray(features, np.uint32).copy()
+        h, w = features.shape[:2]
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        u32 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        worldPos, prevWorldPos, deltaDepth = f32(worldPos), f32(prevWorldPos), f32(deltaDepth)
+        acc, prevMoments = f32(acc), f32(prevMoments)
+        motion = np.zeros((h, w, 2), np.float32) if motion is None else f32(motion).copy()
+        moments = np.zeros((h, w, 4), np.float32) if moments is None else f32(moments).copy()
+        in_, prev = u32(in_), u32(prev)
+        out = np.zeros((h, w, 4), np.float32 if stage == 3 else np.uint32)
+        u = abi.FilterUnit()
+        u.stage, u.w, u.h = int(stage), w, h
+        u.camStationary, u.historyValid, u.lds = int(cam_stationary), int(history_valid), int(lds)
+        u.scale, u.clampDirect, u.clampIndirect = scale, clamp_direct, clamp_indirect
+        if prev_view is not None:
+            u.prevView = prev_view
+            u.view = view if view is not None else prev_view
+        u.acc, u.features, u.worldPos, u.prevWorldPos, u.deltaDepth = ptr(acc), ptr(features), ptr(worldPos), ptr(prevWorldPos), ptr(deltaDepth)
+        u.motion, u.moments, u.prevMoments, u.in_, u.prev, u.out = ptr(motion), ptr(moments), ptr(prevMoments), ptr(in_), ptr(prev), ptr(out)
+        self._chk(self.lib.lh2_core_filter_unit(self.h, C.byref(u)))
+        if stage == 0:
+            return dict(shading=out, motion=motion, moments=moments, features=features)
+        return dict(out=out)
 
     def scene_info(self) -> dict:
         v = [C.c_int(0) for _ in range(4)]

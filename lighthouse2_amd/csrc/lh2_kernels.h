@@ -107,9 +107,14 @@ struct ShadeParams    /* shadeKernel arguments (pathtracer.h:54-59), SoA path st
 	/* the camera fused into the primary packet launch (RenderCore::Render): the first shade launch zeroes the first
 	   hvZeroWords words of the heavy-packet block the frame read, the block the next frame records into */
 	uint32_t* hvZero; uint32_t hvZeroWords;
+	/* filter mode (k_shade's FILT variant, lh2_filter.h): acc holds two planes of w x h (direct, indirect); the first
+	   non-specular vertex of each pixel's sample 0 is recorded into fFeatures / fWorldPos / fDeltaDepth, the depth
+	   derivatives from the view (fPos, fP1, fRight = p2 - p1, fUp = p3 - p1).  Null: off */
+	uint4* fFeatures; float4* fWorldPos; float4* fDeltaDepth;
+	lh2_float3 fPos, fP1, fRight, fUp;
 };
 
-struct TraceArgs      /* one ray stream: rays in, hits (closest) or occlusion (any) out */
+struct TraceArgs     /* one ray stream: rays in, hits (closest) or occlusion (any) out */
 {
 	const float4* rayO; const float4* rayD;
 	/* the rays: a segmented stream (see LH2_SEGS), counts from device memory (segCounts), or, with

@@ -20,6 +20,7 @@
 #include "../../include/lh2_core_types.h"
 #include "lh2_kernels.h"
 #include "lh2_bary.h"
+#include "lh2_filter.h"
 
 #define S_SPECULAR 1
 #define S_BOUNCED 2
@@ -590,7 +591,7 @@ __device__ unsigned long long lh2_shade_tt[16];
 #define LH2_STT_PARAM
 #define LH2_STT_PARAM_DEFAULT
 #endif
-template <bool NL, bool SINGLE, bool EMIT = false>
+template <bool NL, bool SINGLE, bool EMIT = false, bool FILT = false>
 LH2_DEV void shade_path( const SceneDev& s, const ShadeParams& p, const uint4 hd, const float4 T4, const float4 O4, const float4 D4, const float4 Q4,
 	const int pathLength, const uint32_t R0, ShadeOut& o LH2_STT_PARAM_DEFAULT );
 #include "lh2_trace4d.inc"
@@ -1459,10 +1460,40 @@ LH2_DEV float scene_chord( const ShadeParams& p, const float4 o, const float4 d 
 	const float tz = fmaxf( (p.chordLo[2] - o.z) * iz, (p.chordHi[2] - o.z) * iz );
 	return fminf( fminf( tx, ty ), tz );
 }
+/* filter mode (ShadeParams::fFeatures): the records of a pixel's first non-specular vertex (lh2_filter.h; the capture of
+   RenderCore_Optix7Filter's shade kernel).  The history count in features.w stays */
+LH2_DEV void filter_store_empty( const ShadeParams& p, const uint32_t px )
+{
+	p.fFeatures[px] = make_uint4( 0, 0, fbits( LH2_FILTER_MISS_T ), p.fFeatures[px].w & 15u );
+	p.fWorldPos[px] = make_float4( 0, 0, 0, 0 );
+	p.fDeltaDepth[px] = make_float4( 0, 0, 0, 0 );
+}
+LH2_DEV void filter_store( const ShadeParams& p, const uint32_t px, const v3 albedo, const v3 n, const float t, const v3 pos, const uint32_t data,
+	const uint32_t matid )
+{
+	const uint32_t isSpecular = data & S_VIASPECULAR ? 1u : 0u;
+	const uint32_t packedNormal = filter_pack_normal( n.x, n.y, n.z ) + isSpecular;
+	p.fFeatures[px] = make_uint4( filter_pack_rgb( albedo.x, albedo.y, albedo.z ), packedNormal, fbits( t ), filter_features_w( p.fFeatures[px].w, isSpecular, matid ) );
+	p.fWorldPos[px] = make_float4( pos.x, pos.y, pos.z, bitsf( packedNormal ) );
+}
+/* the depth the primary rays of pixels (x + 1, y) and (x, y + 1) would find on the plane (I, N) of the hit, less the
+   hit's (calculateDepthDerivatives) */
+LH2_DEV void filter_store_depth( const ShadeParams& p, const uint32_t px, const float depth, const v3 I, const v3 N )
+{
+	const float fx = (float)(px % (uint32_t)p.w), fy = (float)(px / (uint32_t)p.w);
+	const v3 pos = mk3( p.fPos.x, p.fPos.y, p.fPos.z ), p1 = mk3( p.fP1.x, p.fP1.y, p.fP1.z );
+	const v3 right = mk3( p.fRight.x, p.fRight.y, p.fRight.z ), up = mk3( p.fUp.x, p.fUp.y, p.fUp.z );
+	const float rw = 1.0f / (float)p.w, rh = 1.0f / (float)p.h;
+	const v3 dx = normalize3( sub3( add3( add3( p1, smul( (fx + 0.5f + 1) * rw, right ) ), smul( (fy + 0.5f) * rh, up ) ), pos ) );
+	const v3 dy = normalize3( sub3( add3( add3( p1, smul( (fx + 0.5f) * rw, right ) ), smul( (fy + 0.5f + 1) * rh, up ) ), pos ) );
+	const float num = dot3( sub3( I, pos ), N );
+	p.fDeltaDepth[px] = make_float4( 0, 0, num / dot3( N, dx ) - depth, num / dot3( N, dy ) - depth );
+}
+
 /* one path vertex of shadeKernel (pathtracer.h:54-245): the hit record, ray and path state of a path at
    pathLength in; its extension ray (o.ext) and shadow ray (o.shadow) out.  Shared by k_shade (one launch
    per bounce) and the path-tail kernel (k_trace_path4d: trace and shade in one loop per lane) */
-template <bool NL, bool SINGLE, bool EMIT>
+template <bool NL, bool SINGLE, bool EMIT, bool FILT>
 LH2_DEV void shade_path( const SceneDev& s, const ShadeParams& p, const uint4 hd, const float4 T4, const float4 O4, const float4 D4, const float4 Q4,
 	const int pathLength, const uint32_t R0, ShadeOut& o LH2_STT_PARAM )
 {
@@ -1479,6 +1510,10 @@ LH2_DEV void shade_path( const SceneDev& s, const ShadeParams& p, const uint4 hd
 	const uint32_t pathIdx = data >> 8;
 	const uint32_t pixelIdx = pathIdx % (uint32_t)(w * h);
 	const uint32_t sampleIdx = pathIdx / (uint32_t)(w * h) + (uint32_t)p.pass;
+	/* filter mode: light gathered after the first diffuse bounce goes to the accumulator's second plane (indirect);
+	   the pixel's sample 0 records its first non-specular vertex (storeFeat) */
+	const uint32_t accIdx = FILT && (data & S_BOUNCED) ? pixelIdx + (uint32_t)(w * h) : pixelIdx;
+	const bool storeFeat = FILT && !(data & S_BOUNCED) && pathIdx < (uint32_t)(w * h);
 	/* this vertex's blue-noise samples (dimensions 4..7 + 4 pathLength: r0, r1 for the light, r3, r4
 	   for the BSDF) and the hit's instance record are fetched together, and the sample bytes with
 	   the triangle: the dependent chain is inputs -> (ranking bytes, instance) -> (samples,
@@ -1503,12 +1538,16 @@ LH2_DEV void shade_path( const SceneDev& s, const ShadeParams& p, const uint4 hd
 	blueNoiseFinish4( s.blueNoise, bnq, bnv );
 	LH2_STT( 0 )
 	if (pathLength == 1) unsafeAtomicAdd( &p.acc[pixelIdx].w, PRIMIDX == NOHIT ? 10000.0f : HIT_T );
+	if (FILT && storeFeat && pathLength == 1) filter_store_empty( p, pixelIdx );
 	if (PRIMIDX == NOHIT)
 	{
 		v3 contribution = muls( mul3( throughput, SampleSkydome( s, D ) ), 1.0f / bsdfPdf );
 		contribution = clampintensity( s.clampValue, contribution );
 		contribution = fixnan( contribution );
-		acc_add( p.acc, pixelIdx, contribution );
+		acc_add( p.acc, accIdx, contribution );
+		/* the path leaves the scene: the sky's colour as albedo, a vertex far along the ray */
+		if (FILT && storeFeat)
+			filter_store( p, pixelIdx, contribution, muls( D, -1.0f ), LH2_FILTER_MISS_T, add3( RAY_O, smul( 50000.0f, D ) ), data, 0 );
 		return;
 	}
 	if ((int)pixelIdx == p.probePixel && pathLength == 1 && sampleIdx == 0)
@@ -1529,6 +1568,7 @@ LH2_DEV void shade_path( const SceneDev& s, const ShadeParams& p, const uint4 hd
 				o.eO = make_float4( I.x, I.y, I.z, EPSILON ), o.eD = make_float4( D.x, D.y, D.z, 1e34f );
 				o.eT = make_float4( throughput.x, throughput.y, throughput.z, bitsf( data ) ), o.eQ = make_float4( bsdfPdf, 0, 0, 0 );
 			}
+			else if (FILT && storeFeat) filter_store( p, pixelIdx, s3( 0 ), N, HIT_T, I, data, 0 );   /* a cut-out at the last vertex */
 			return;
 		}
 		if (sd.color.x > 1.0f || sd.color.y > 1.0f || sd.color.z > 1.0f)
@@ -1548,13 +1588,30 @@ LH2_DEV void shade_path( const SceneDev& s, const ShadeParams& p, const uint4 hd
 				}
 				contribution = clampintensity( s.clampValue, contribution );
 				contribution = fixnan( contribution );
-				acc_add( p.acc, pixelIdx, contribution );
+				acc_add( p.acc, accIdx, contribution );
+			}
+			if (FILT && storeFeat)
+			{
+				filter_store( p, pixelIdx, sd.color, N, HIT_T, I, data, (uint32_t)__float_as_int( tq.t1.w ) );
+				filter_store_depth( p, pixelIdx, HIT_T, I, N );
 			}
 			return;
 		}
 		if (ROUGHNESS <= 0.001f || TRANSMISSION > 0.999f) data |= S_SPECULAR; else data &= ~S_SPECULAR;
 		uint32_t seed = WangHash( pathIdx * 17 + R0 );
 		const float faceDir = (dot3( D, N ) > 0) ? -1 : 1;
+		if (FILT && storeFeat)
+		{
+			/* a pure specular vertex leaves its colour for the first diffuse one, which multiplies it in */
+			if (data & S_SPECULAR) p.fFeatures[pixelIdx].x = filter_pack_rgb( sd.color.x, sd.color.y, sd.color.z );
+			else
+			{
+				v3 albedo = sd.color;
+				if (data & S_VIASPECULAR) { v3 c; filter_unpack_rgb( p.fFeatures[pixelIdx].x, c.x, c.y, c.z ); albedo = mul3( albedo, c ); }
+				filter_store( p, pixelIdx, albedo, muls( fN, faceDir ), HIT_T, I, data, (uint32_t)__float_as_int( tq.t1.w ) );
+				filter_store_depth( p, pixelIdx, HIT_T, I, N );
+			}
+		}
 		if (faceDir == 1) sd.transmittance = s3( 0 );
 		throughput = muls( throughput, 1.0f / bsdfPdf );
 		if (NL && !(data & S_SPECULAR) && sampleIdx >= 2) (void)RandomFloat( seed ), (void)RandomFloat( seed );
@@ -1585,7 +1642,7 @@ LH2_DEV void shade_path( const SceneDev& s, const ShadeParams& p, const uint4 hd
 					contribution = clampintensity( s.clampValue, contribution );
 					const v3 so = SafeOrigin( I, L, muls( N, faceDir ), s.geometryEpsilon );
 					const float4 sO = make_float4( so.x, so.y, so.z, 0 ), sD = make_float4( L.x, L.y, L.z, dist - 2 * s.geometryEpsilon );
-					const float4 sP = make_float4( contribution.x, contribution.y, contribution.z, __uint_as_float( pixelIdx ) );
+					const float4 sP = make_float4( contribution.x, contribution.y, contribution.z, __uint_as_float( accIdx ) );
 					if (EMIT)
 					{
 						/* k_shade (round 6): the shadow ray goes into the block's shadow segment here, one atomic for the lanes
@@ -1613,6 +1670,8 @@ LH2_DEV void shade_path( const SceneDev& s, const ShadeParams& p, const uint4 hd
 			}
 		}
 		LH2_STT( 4 )
+		/* (filter mode: a specular chain that ends at the last vertex keeps what is known of it) */
+		if (FILT && storeFeat && (data & S_SPECULAR) && pathLength == p.maxPathLength) filter_store( p, pixelIdx, s3( 0 ), N, HIT_T, I, data, 0 );
 		if (data & ENOUGH_BOUNCES || pathLength == p.maxPathLength) return;
 		{
 			v3 R = s3( 0 );
@@ -1663,7 +1722,7 @@ LH2_DEV void shade_epilogue( const ShadeParams& p );   /* the bounce hand-off, b
 /* NL: a scene without lights.  NEE (pathtracer.h:168-208) then never yields a shadow ray
    (RandomPointOnLight: lightPdf 0), so its code is compiled out, except the two random numbers it
    draws past sample 1, which later draws depend on */
-template <bool TERM, bool NL, bool SINGLE>
+template <bool TERM, bool NL, bool SINGLE, bool FILT = false>
 __global__ __launch_bounds__( 256, NL ? LH2_SHADE_NL_MINWAVES : LH2_SHADE_MINWAVES ) void k_shade( const SceneDev s, const ShadeParams p )
 {
 	/* the block's segment of the path stream (its XCD's), and the segment's share of the grid */
@@ -1697,9 +1756,9 @@ __global__ __launch_bounds__( 256, NL ? LH2_SHADE_NL_MINWAVES : LH2_SHADE_MINWAV
 			ShadeOut so;
 			so.ext = so.shadow = false, so.seg = seg;
 #ifdef LH2_SHADE_TIMES
-			shade_path<NL, SINGLE, LH2_SHADE_EMIT != 0>( s, p, hd, T4, O4, D4, Q4, p.pathLength, p.R0, so, &stt );
+			shade_path<NL, SINGLE, LH2_SHADE_EMIT != 0, FILT>( s, p, hd, T4, O4, D4, Q4, p.pathLength, p.R0, so, &stt );
 #else
-			shade_path<NL, SINGLE, LH2_SHADE_EMIT != 0>( s, p, hd, T4, O4, D4, Q4, p.pathLength, p.R0, so );
+			shade_path<NL, SINGLE, LH2_SHADE_EMIT != 0, FILT>( s, p, hd, T4, O4, D4, Q4, p.pathLength, p.R0, so );
 #endif
 			doExt = so.ext, doShadow = so.shadow;
 			eO = so.eO, eD = so.eD, eT = so.eT, eQ = so.eQ, sO = so.sO, sD = so.sD, sP = so.sP;
@@ -2246,6 +2305,14 @@ void lh2_launch_shade( const SceneDev* s, const ShadeParams* p, int grid, Launch
 {
 	grid = grid < LH2_SEGS ? LH2_SEGS : grid;   /* every segment needs a block */
 	if (p->primeRef) LH2_LAUNCH( k_shade_ref, grid, 256, st, ev, *s, *p );
+	else if (p->fFeatures)   /* filter mode: the capture variants (never terminal: RenderCore::Render) */
+	{
+		const bool nl = s->nArea + s->nPoint + s->nSpot + s->nDir == 0;
+		if (s->tris0 && nl) LH2_LAUNCH( (k_shade<false, true, true, true>), grid, 256, st, ev, *s, *p );
+		else if (s->tris0) LH2_LAUNCH( (k_shade<false, false, true, true>), grid, 256, st, ev, *s, *p );
+		else if (nl) LH2_LAUNCH( (k_shade<false, true, false, true>), grid, 256, st, ev, *s, *p );
+		else LH2_LAUNCH( (k_shade<false, false, false, true>), grid, 256, st, ev, *s, *p );
+	}
 	else if (p->terminal && p->pathLength == p->maxPathLength) LH2_LAUNCH( k_shade_last, lh2_shade_last_grid(), 256, st, ev, *s, *p );
 	else if (s->tris0)   /* one instance (SceneDev::tris0): the triangle loads need no instance record */
 	{

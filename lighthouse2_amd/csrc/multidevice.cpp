@@ -15,6 +15,8 @@ MultiDevice::MultiDevice( RenderCore* primary, int count )
 	MD_CHK( hipGetDeviceCount( &physical ) );
 	const int d0 = primary->Device();
 	cores.push_back( primary ), devices.push_back( d0 );
+	/* no denoise mode over several devices: a band has no neighbours across its edge (the setting "filter" then reads 0) */
+	primary->SetFilterAllowed( false );
 	for (int i = 1; i < count; i++)
 	{
 		const int d = (d0 + i) % std::max( 1, physical );
@@ -29,6 +31,7 @@ MultiDevice::MultiDevice( RenderCore* primary, int count )
 		}
 		RenderCore* c = new RenderCore();
 		c->Init();
+		c->SetFilterAllowed( false );
 		cores.push_back( c ), devices.push_back( d );
 	}
 	MD_CHK( hipSetDevice( d0 ) );
@@ -76,6 +79,7 @@ MultiDevice::~MultiDevice()
 		if (i > 0) { (void)hipSetDevice( devices[i] ); cores[i]->Shutdown(); delete cores[i]; }
 	}
 	(void)hipSetDevice( devices[0] );
+	try { cores[0]->SetFilterAllowed( true ); } catch (...) {}   /* one device again: the setting "filter" counts */
 }
 
 /* ---- worker pool: one host thread per sub-core, its device current ---------------------- */

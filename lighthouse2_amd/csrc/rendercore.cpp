@@ -168,6 +168,7 @@ void RenderCore::SetTarget( uint32_t w, uint32_t h, uint32_t spp )  /* rendercor
 	CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * (size_t)w * h, stream ) );
 	CHK_HIP( hipMemsetAsync( delta.ptr, 0, sizeof( float4 ) * 2 * (size_t)w * h, stream ) );
 	samplesTaken = 0;
+	fl.historyValid = false;   /* the denoise mode starts over */
 }
 
 /* display output (interoptexture.cpp:25-71): register the app's GL_RGBA32F texture with HIP once per
@@ -201,9 +202,39 @@ int RenderCore::TraceVersion() const { return (traceVersion == 1 || !bvh4) ? 1 :
 
 void RenderCore::EnsureBuffers()
 {
-	accumulator.resize( (size_t)scrwidth * scrheight );
+	accumulator.resize( (FilterOn() ? 2 : 1) * (size_t)scrwidth * scrheight );   /* the denoise mode: direct and indirect planes */
 	frame.resize( (size_t)scrwidth * scrheight );
 	delta.resize( 2 * (size_t)scrwidth * scrheight );   /* per frame parity: the next frame's first shade may run beside this finalize */
+	if (FilterOn()) EnsureFilterBuffers();
+}
+
+/* the denoise mode's buffers, for the current target; a new size starts without history */
+void RenderCore::EnsureFilterBuffers()
+{
+	const size_t n = (size_t)scrwidth * scrheight;
+	if (!fl.ev[0]) for (auto& e : fl.ev) CHK_HIP( hipEventCreate( &e ) );
+	if (fl.pixels == n || !n) return;
+	fl.features.resize( n ), fl.deltaDepth.resize( n ), fl.shading.resize( n ), fl.motion.resize( n );
+	for (int i = 0; i < 2; i++) fl.worldPos[i].resize( n ), fl.moments[i].resize( n ), fl.filtered[i].resize( n );
+	/* the history counts start at 0, and no record is read before it was written */
+	CHK_HIP( hipMemsetAsync( fl.features.ptr, 0, sizeof( uint4 ) * n, stream ) );
+	for (int i = 0; i < 2; i++)
+	{
+		CHK_HIP( hipMemsetAsync( fl.worldPos[i].ptr, 0, sizeof( float4 ) * n, stream ) );
+		CHK_HIP( hipMemsetAsync( fl.moments[i].ptr, 0, sizeof( float4 ) * n, stream ) );
+		CHK_HIP( hipMemsetAsync( fl.filtered[i].ptr, 0, sizeof( float4 ) * n, stream ) );
+	}
+	fl.pixels = n, fl.historyValid = false, fl.cur = 0;
+}
+
+/* the denoise mode allowed or not (MultiDevice): as if the setting "filter" changed */
+void RenderCore::SetFilterAllowed( bool on )
+{
+	if (on == filterAllowed) return;
+	const bool want = filterOn;
+	Setting( "filter", 0.0f );   /* off under the old permission: frees the buffers if it was on */
+	filterAllowed = on;
+	Setting( "filter", want ? 1.0f : 0.0f );
 }
 
 /* path buffers for `paths` paths (a bit extra, as the reference reserves, and room for LH2_SEGS segments
@@ -289,7 +320,41 @@ void RenderCore::Setting( const char* name, float value )  /* rendercore.cpp:439
 	}
 	else if (!strcmp( name, "unitCoherent" )) unitCoherent = value != 0;   /* TraceClosestDevice traces as the frame traces primary rays */
 	else if (!strcmp( name, "traceVersion" )) traceVersion = (int)value == 1 ? 1 : 0;   /* 1: the reference BVH2 loop; else the BVH4 loop */
-	/* other names ("clampDirect", "filter", "TAA", ...) are ignored, as in the reference */
+	/* the denoise mode (SVGF: lh2_filter.h): every Render delivers a filtered frame of that frame's samples and the
+	   reprojected history; the light clamps are those of its prepare step */
+	else if (!strcmp( name, "filter" ))
+	{
+		const bool was = FilterOn();
+		filterOn = value != 0;
+		const bool now = FilterOn();
+		if (was != now && initialized)
+		{
+			/* the frames in flight end; the accumulator gets or loses its second plane, the filter's buffers come or go, and
+			   the next frame starts the accumulation over */
+			CHK_HIP( hipStreamSynchronize( aheadStream ) );
+			CHK_HIP( hipStreamSynchronize( sideStream ) );
+			CHK_HIP( hipStreamSynchronize( stream ) );
+			if (!now)
+			{
+				fl.features.free(), fl.deltaDepth.free(), fl.shading.free(), fl.motion.free();
+				for (int i = 0; i < 2; i++) fl.worldPos[i].free(), fl.moments[i].free(), fl.filtered[i].free();
+				fl.pixels = 0, fl.historyValid = false;
+			}
+			if (scrwidth)
+			{
+				accumulator.free();
+				EnsureBuffers();
+				CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * accumulator.count, stream ) );
+				sceneVersion++;
+			}
+			samplesTaken = 0, firstConvergingFrame = true;
+		}
+	}
+	else if (!strcmp( name, "clampDirect" )) clampDirect = value;
+	else if (!strcmp( name, "clampIndirect" )) clampIndirect = value;
+	/* the a-trous passes' taps: 1 from an LDS tile, 0 through L1 / L2, -1 the measured pick per pass (RunFilter) */
+	else if (!strcmp( name, "filterLds" )) filterLds = value < 0 ? -1 : value != 0;
+	/* other names ("TAA", ...) are ignored, as in the reference */
 }
 
 /* the current value of a setting (extension: the reference has no getter); false for unknown names */
@@ -306,7 +371,8 @@ bool RenderCore::GetSetting( const char* name, float& value ) const
 		{ "pathTailWaves", (float)pathTailWaves }, { "packetPrimary", (float)packetPrimary }, { "singleInstanceStart", (float)singleInstanceStart },
 		{ "terminalShade", (float)terminalShade }, { "traceBlocksPerCU", (float)ClosestBlocksPerCU( ScenePicksWaves() ) }, { "unitTraceWaves", (float)unitTraceWaves }, { "traceWaves", (float)traceWaves },
 		{ "unitCoherent", (float)unitCoherent }, { "traceVersion", (float)TraceVersion() },
-		{ "usePackets", (float)UsePackets() }, { "blasBuilds", (float)BlasBuildCount() } };
+		{ "usePackets", (float)UsePackets() }, { "blasBuilds", (float)BlasBuildCount() },
+		{ "filter", (float)FilterOn() }, { "clampDirect", clampDirect }, { "clampIndirect", clampIndirect }, { "filterLds", (float)filterLds } };
 	for (const auto& e : t) if (!strcmp( name, e.n )) { value = e.v; return true; }
 	return false;
 }
@@ -951,6 +1017,13 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 	if (converge == LH2_CONVERGE) firstConvergingFrame = false;
 	const int tileRows = TileRows();
 	const uint32_t pathCount = (uint32_t)tileRows * (uint32_t)scrwidth * (uint32_t)scrspp;
+	/* the denoise mode (whole frames only: a tile has no neighbours across its edge; not in PrimeRef mode): the plain
+	   wavefront loop, one launch pair per bounce behind the previous frame - no path tail, no early or terminal shade, no
+	   overlap of consecutive frames; the accumulator (two planes) holds this frame's samples only, and the lens is a pinhole */
+	const bool filt = FilterOn() && fl.pixels && tileRows == scrheight && !primeRef;
+	/* converge == Restart resets the history (the first converging frame after it restarts the accumulation too, as in the
+	   reference, but keeps the history) */
+	if (filt && converge == LH2_RESTART) fl.historyValid = false;
 	const SceneDev sd = MakeSceneDev();
 	const int frameTlas = tlasSlot;   /* the TLAS slot this frame reads (evTlasFree after its finalize) */
 	/* the accumulator reset of a restart is folded into the camera launch (each pixel's first sample zeroes
@@ -980,7 +1053,7 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 	cp.pos = view.pos, cp.p1 = view.p1;
 	cp.right = { view.p2.x - view.p1.x, view.p2.y - view.p1.y, view.p2.z - view.p1.z };
 	cp.up = { view.p3.x - view.p1.x, view.p3.y - view.p1.y, view.p3.z - view.p1.z };
-	cp.aperture = view.aperture, cp.distortion = view.distortion, cp.geometryEpsilon = geometryEpsilon;
+	cp.aperture = filt ? 0.0f : view.aperture, cp.distortion = view.distortion, cp.geometryEpsilon = geometryEpsilon;
 	cp.w = scrwidth, cp.h = scrheight, cp.pass = samplesTaken;
 	cp.R0 = XorShift( camRNGseed );
 	cp.y0 = std::max( 0, tileY0 ), cp.tileRows = tileRows;
@@ -990,6 +1063,11 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 	cp.initC = c, cp.cursors = cursors, cp.cursorWords = LH2_CURSOR_SLOTS * LH2_CURSOR_WORDS;
 	cp.pathCount = pathCount, cp.segStride = ps.segStride;
 	cp.clearAcc = restart && !tileChanged ? accumulator.ptr : nullptr;
+	if (filt)
+	{
+		CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * 2 * (size_t)scrwidth * scrheight, stream ) );
+		cp.clearAcc = nullptr;
+	}
 	/* heavy-first primary packets: this frame reads the block the previous one recorded, and records into the
 	   other one, which the camera launch zeroes (a new layout zeroes both) */
 	ps.hvOn = packetHeavy != 0 && tiledRays && UsePackets() && !primeRef;
@@ -1024,7 +1102,7 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 	/* the primary stage beside the previous frame (frame overlap), or behind it on the core stream: on a restart (the
 	   launch zeroes accumulator pixels), after a change of scene data, buffers or tile, or when the previous frame had no
 	   such primary stage */
-	const bool serialize = !frameOverlap || !ps.lastFused || ps.relaid || tileChanged || sceneVersion != ps.lastSceneVersion;
+	const bool serialize = filt || !frameOverlap || !ps.lastFused || ps.relaid || tileChanged || sceneVersion != ps.lastSceneVersion;
 	/* a restart beside the previous frame: the accumulator is zeroed on the core stream, behind the previous frame's finalize
 	   and before this frame's first addition there (the early shade adds into the delta), not by the primary launch */
 	if (pFrame && !serialize && cp.clearAcc)
@@ -1069,7 +1147,7 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 	   so the bounce after it would be empty; not launching it saves three launches (~25 us) */
 	if (!primeRef && diffuseOnly) maxPL = std::min( maxPL, 2 );
 	/* the path tail (setting "pathTail"): bounces pathTail .. maxPL in one launch of k_trace_path4d */
-	const int tailL = (!primeRef && pathTail >= 2 && pathTail <= maxPL && TraceVersion() == 7) ? pathTail : 0;
+	const int tailL = (!primeRef && !filt && pathTail >= 2 && pathTail <= maxPL && TraceVersion() == 7) ? pathTail : 0;
 	/* early shade: the first shade launch follows the primary launch on the ahead stream and writes the ping-pong buffer
 	   the previous frame's launches after its overlap event do not use (PathStreams::busy / earlyOk).  Only when this
 	   frame has a path tail from bounce 3 on: else its first shade launch is its overlap event (and, with the tail from
@@ -1146,6 +1224,11 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 		sp.w = scrwidth, sp.h = scrheight, sp.pass = samplesTaken, sp.pathLength = pathLength, sp.maxPathLength = maxPL;
 		sp.probePixel = probeX + scrwidth * probeY;
 		sp.spreadAngle = view.spreadAngle;
+		if (filt)
+		{
+			sp.fFeatures = fl.features.ptr, sp.fWorldPos = fl.worldPos[fl.cur].ptr, sp.fDeltaDepth = fl.deltaDepth.ptr;
+			sp.fPos = cp.pos, sp.fP1 = cp.p1, sp.fRight = cp.right, sp.fUp = cp.up;
+		}
 		if (pathLength == tailL)
 		{
 			/* the path tail: trace and shade every remaining bounce in one launch; each path's records are
@@ -1243,7 +1326,7 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 		if (fusedPrimary) sp.rayO = ps.rayOP[ps.fp].ptr, sp.rayD = ps.rayDP[ps.fp].ptr, sp.T4 = ps.T4P[ps.fp].ptr, sp.Q4 = ps.Q4P[ps.fp].ptr, sp.hits = ps.hitsP[ps.fp].ptr;
 		sp.rayOut = ps.rayO[1 - ps.in].ptr, sp.rayDOut = ps.rayD[1 - ps.in].ptr, sp.T4Out = ps.T4[1 - ps.in].ptr, sp.Q4Out = ps.Q4[1 - ps.in].ptr;
 		sp.primeRef = primeRef;
-		sp.terminal = !primeRef && !shadows && !canEmit && pathLength > 1 && terminalShade;
+		sp.terminal = !primeRef && !filt && !shadows && !canEmit && pathLength > 1 && terminalShade;
 		sp.R0 = (uint32_t)samplesTaken * 7907u + (uint32_t)pathLength * 91771u;
 		if (pathLength == 1 && fusedCam && hvReadBlock)
 		{
@@ -1338,7 +1421,16 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 	   its primary launch's start and the previous frame's end (Synchronize), so per-frame times sum to wall time */
 	std::swap( evFrame[1], evFrame[2] );
 	prevFrameEndValid = frameEndRecorded, frameWasOverlapped = pFrame && !serialize;
-	lh2_launch_finalize( accumulator.ptr, frame.ptr, scrwidth * scrheight, 1.0f / (float)samplesTaken, &fs, { nullptr, evFrame[1] }, stream, &rm );
+	frameFiltered = filt;
+	if (filt)
+	{
+		/* the filter chain writes the frame; the finalize launch only delivers the statistics (no pixels).  The next frame stays
+		   behind this one */
+		RunFilter( view );
+		lh2_launch_finalize( accumulator.ptr, frame.ptr, 0, 1.0f, &fs, { nullptr, evFrame[1] }, stream, nullptr );
+		ps.relaid = true;
+	}
+	else lh2_launch_finalize( accumulator.ptr, frame.ptr, scrwidth * scrheight, 1.0f / (float)samplesTaken, &fs, { nullptr, evFrame[1] }, stream, &rm );
 	frameEndRecorded = true;
 	CHK_HIP( hipEventRecord( evTlasFree[frameTlas], stream ) );   /* the next update of this TLAS slot waits for it */
 	tlasFreeValid[frameTlas] = true;
@@ -1356,6 +1448,119 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 	framePrimeRef = primeRef;
 	statsPending = true;
 	frameHostMs = std::chrono::duration<double, std::milli>( std::chrono::high_resolution_clock::now() - t0 ).count();
+}
+
+/* the denoise chain of a frame (reference rendercore.cpp:827-862): prepare, three a-trous passes (the last one writes the
+   frame), then the buffers change roles for the next frame */
+void RenderCore::RunFilter( const lh2_ViewPyramid& view )
+{
+	const int c = fl.cur, q = 1 - c;
+	CHK_HIP( hipEventRecord( fl.ev[0], stream ) );
+	FilterPrepareArgs pa{};
+	pa.acc = accumulator.ptr, pa.features = fl.features.ptr;
+	pa.worldPos = fl.worldPos[c].ptr, pa.prevWorldPos = fl.worldPos[q].ptr, pa.deltaDepth = fl.deltaDepth.ptr;
+	pa.prevMoments = fl.moments[q].ptr;
+	pa.shading = fl.shading.ptr, pa.motion = fl.motion.ptr, pa.moments = fl.moments[c].ptr;
+	lh2_filter_view( fl.historyValid ? &fl.prevView : &view, scrheight, pa.prevView );
+	lh2_filter_view( &view, scrheight, pa.curView );
+	pa.w = scrwidth, pa.h = scrheight, pa.scale = 1.0f / (float)scrspp;
+	pa.clampDirect = clampDirect, pa.clampIndirect = clampIndirect;
+	pa.camStationary = !fl.historyValid || !memcmp( &fl.prevView, &view, sizeof( lh2_float3 ) * 4 );
+	pa.historyValid = fl.historyValid;
+	lh2_launch_filter_prepare( &pa, { nullptr, fl.ev[1] }, stream );
+	FilterAtrousArgs aa{};
+	aa.features = fl.features.ptr, aa.worldPos = fl.worldPos[c].ptr, aa.prevWorldPos = fl.worldPos[q].ptr, aa.deltaDepth = fl.deltaDepth.ptr;
+	aa.motion = fl.motion.ptr, aa.moments = fl.moments[c].ptr;
+	aa.w = scrwidth, aa.h = scrheight, aa.historyValid = fl.historyValid;
+	/* filtered[q] holds the previous frame's first pass: this frame's goes to filtered[c], the second pass then overwrites
+	   filtered[q], and the third writes the frame */
+	float4* const in[3] = { fl.shading.ptr, fl.filtered[c].ptr, fl.filtered[q].ptr };
+	float4* const out[3] = { fl.filtered[c].ptr, fl.filtered[q].ptr, frame.ptr };
+	for (int phase = 1; phase <= 3; phase++)
+	{
+		aa.phase = phase, aa.A = in[phase - 1], aa.B = phase == 1 ? fl.filtered[q].ptr : nullptr, aa.C = out[phase - 1];
+		aa.lds = filterLds >= 0 ? filterLds : kFilterLdsPick[phase - 1];
+		lh2_launch_filter_atrous( &aa, { nullptr, fl.ev[phase + 1] }, stream );
+	}
+	/* the next frame: worldPos, moments and the first pass's output become its history (the swaps of rendercore.cpp:856-862) */
+	fl.cur = q, fl.historyValid = true, fl.prevView = view;
+}
+
+void RenderCore::GetFilterBuffer( int which, void* out )
+{
+	Synchronize();
+	if (!fl.pixels) FatalError( "the denoise mode is off (setting \"filter\"): it has no buffers" );
+	const size_t n = fl.pixels;
+	const int c = 1 - fl.cur, q = fl.cur;   /* the last frame's buffers, and the ones of the frame before it */
+	const void* src = nullptr;
+	size_t bytes = 16 * n;
+	switch (which)
+	{
+	case LH2_FILTER_BUF_ACC: src = accumulator.ptr, bytes = 32 * n; break;
+	case LH2_FILTER_BUF_FEATURES: src = fl.features.ptr; break;
+	case LH2_FILTER_BUF_WORLDPOS: src = fl.worldPos[c].ptr; break;
+	case LH2_FILTER_BUF_DELTADEPTH: src = fl.deltaDepth.ptr; break;
+	case LH2_FILTER_BUF_MOTION: src = fl.motion.ptr, bytes = 8 * n; break;
+	case LH2_FILTER_BUF_MOMENTS: src = fl.moments[c].ptr; break;
+	case LH2_FILTER_BUF_SHADING: src = fl.shading.ptr; break;
+	case LH2_FILTER_BUF_PHASE1: src = fl.filtered[c].ptr; break;
+	case LH2_FILTER_BUF_PHASE2: src = fl.filtered[q].ptr; break;
+	case LH2_FILTER_BUF_PHASE3: src = frame.ptr; break;
+	case LH2_FILTER_BUF_PREVWORLDPOS: src = fl.worldPos[q].ptr; break;
+	case LH2_FILTER_BUF_PREVMOMENTS: src = fl.moments[q].ptr; break;
+	default: FatalError( "unknown filter buffer %d", which );
+	}
+	CHK_HIP( hipMemcpy( out, src, bytes, hipMemcpyDeviceToHost ) );
+}
+void RenderCore::GetFilterTimes( float* ms4 )
+{
+	Synchronize();
+	for (int k = 0; k < 4; k++) ms4[k] = frameFiltered ? fl.ms[k] : 0.0f;
+}
+
+/* one kernel of the chain on host arrays (lh2_FilterUnit): uploads what the stage reads, runs it, copies back what it writes */
+void RenderCore::FilterUnit( const lh2_FilterUnit& u )
+{
+	if (u.w < 1 || u.h < 1 || (uint64_t)u.w * u.h > (1u << 26) || u.stage < 0 || u.stage > 3) FatalError( "bad filter unit: stage %d, %d x %d", u.stage, u.w, u.h );
+	const size_t n = (size_t)u.w * u.h;
+	auto need = []( const void* p, const char* what ) { if (!p) FatalError( "filter unit: %s is null", what ); };
+	need( u.features, "features" ), need( u.worldPos, "worldPos" ), need( u.prevWorldPos, "prevWorldPos" ), need( u.deltaDepth, "deltaDepth" );
+	need( u.motion, "motion" ), need( u.moments, "moments" ), need( u.out, "out" );
+	DevBuf<uint4> features; DevBuf<float4> worldPos, prevWorldPos, deltaDepth, moments, prevMoments, acc, in, prev, out; DevBuf<float2> motion;
+	features.upload( (const uint4*)u.features, n, stream ), worldPos.upload( (const float4*)u.worldPos, n, stream );
+	prevWorldPos.upload( (const float4*)u.prevWorldPos, n, stream ), deltaDepth.upload( (const float4*)u.deltaDepth, n, stream );
+	out.resize( n ), motion.resize( n ), moments.resize( n );
+	if (u.stage == 0)
+	{
+		need( u.acc, "acc" ), need( u.prevMoments, "prevMoments" );
+		acc.upload( (const float4*)u.acc, 2 * n, stream ), prevMoments.upload( (const float4*)u.prevMoments, n, stream );
+		FilterPrepareArgs pa{};
+		pa.acc = acc.ptr, pa.features = features.ptr, pa.worldPos = worldPos.ptr, pa.prevWorldPos = prevWorldPos.ptr, pa.deltaDepth = deltaDepth.ptr;
+		pa.prevMoments = prevMoments.ptr, pa.shading = out.ptr, pa.motion = motion.ptr, pa.moments = moments.ptr;
+		lh2_filter_view( &u.prevView, u.h, pa.prevView );
+		lh2_filter_view( &u.view, u.h, pa.curView );
+		pa.w = u.w, pa.h = u.h, pa.scale = u.scale, pa.clampDirect = u.clampDirect, pa.clampIndirect = u.clampIndirect;
+		pa.camStationary = u.camStationary, pa.historyValid = u.historyValid;
+		lh2_launch_filter_prepare( &pa, {}, stream );
+		CHK_HIP( hipMemcpyAsync( u.features, features.ptr, sizeof( uint4 ) * n, hipMemcpyDeviceToHost, stream ) );
+		CHK_HIP( hipMemcpyAsync( u.motion, motion.ptr, sizeof( float2 ) * n, hipMemcpyDeviceToHost, stream ) );
+		CHK_HIP( hipMemcpyAsync( u.moments, moments.ptr, sizeof( float4 ) * n, hipMemcpyDeviceToHost, stream ) );
+	}
+	else
+	{
+		need( u.in, "in" );
+		if (u.stage == 1) need( u.prev, "prev" );
+		motion.upload( (const float2*)u.motion, n, stream ), moments.upload( (const float4*)u.moments, n, stream );
+		in.upload( (const float4*)u.in, n, stream );
+		if (u.stage == 1) prev.upload( (const float4*)u.prev, n, stream );
+		FilterAtrousArgs aa{};
+		aa.features = features.ptr, aa.worldPos = worldPos.ptr, aa.prevWorldPos = prevWorldPos.ptr, aa.deltaDepth = deltaDepth.ptr;
+		aa.motion = motion.ptr, aa.moments = moments.ptr, aa.A = in.ptr, aa.B = u.stage == 1 ? prev.ptr : nullptr, aa.C = out.ptr;
+		aa.w = u.w, aa.h = u.h, aa.phase = u.stage, aa.historyValid = u.historyValid, aa.lds = u.lds;
+		lh2_launch_filter_atrous( &aa, {}, stream );
+	}
+	CHK_HIP( hipMemcpyAsync( u.out, out.ptr, sizeof( float4 ) * n, hipMemcpyDeviceToHost, stream ) );
+	CHK_HIP( hipStreamSynchronize( stream ) );
 }
 
 void RenderCore::UnpackTile( const void* devSrc, int rank, int nranks, int band )
@@ -1448,6 +1653,12 @@ void RenderCore::Synchronize()
 	for (int L = 1; L <= ps.pl; L++) if (L != ps.tailL) shade += ms( ps.fromShade[L], ps.evShade[L] );
 	coreStats.shadowTraceTime = shadow;
 	coreStats.shadeTime = shade;
+	coreStats.filterTime = 0;
+	if (frameFiltered)
+	{
+		coreStats.filterTime = ms( fl.ev[0], fl.ev[4] );
+		for (int k = 0; k < 4; k++) fl.ms[k] = ms( fl.ev[k], fl.ev[k + 1] ) * 1e3f;
+	}
 	for (int L = 1; L <= framePathLengths && L <= 8; L++) lastKernelMs[L - 1] = trace( L ) * 1e3f;
 	coreStats.totalShadowRays = framePrimeRef ? cn.totalShadowRays : QueuedShadowRays( cn );
 	coreStats.totalExtensionRays = cn.totalExtensionRays;
@@ -1752,6 +1963,7 @@ void RenderCore::Shutdown()   /* rendercore.cpp:615-650 */
 	if (ps.activeLog) (void)hipHostFree( ps.activeLog );
 	ps.activeLog = nullptr;
 	for (hipEvent_t* e : { &evConsumer, &evPacked }) { if (*e) (void)hipEventDestroy( *e ); *e = nullptr; }
+	for (auto& e : fl.ev) { if (e) (void)hipEventDestroy( e ); e = nullptr; }
 	for (auto& e : evFrame) (void)hipEventDestroy( e );
 	for (auto& e : evStage) (void)hipEventDestroy( e );
 	for (hipEvent_t* e : { &evTlasReady, &evTlasFree[0], &evTlasFree[1] }) { if (*e) (void)hipEventDestroy( *e ); *e = nullptr; }

@@ -11,9 +11,11 @@
 #include <vector>
 
 #include "../../include/lh2_core_types.h"
+#include "../../include/lh2_rendercore.h"
 #include "bvh_build.h"
 #include "bvh_gpu.h"
 #include "lh2_kernels.h"
+#include "lh2_filter.h"
 #include "lh2_device.h"
 
 namespace lh2 {
@@ -130,6 +132,22 @@ struct PathStreams
 	bool earlyOk = false, early = false;
 };
 
+/* the denoise mode's buffers (setting "filter"; lh2_filter.h), allocated only while it is on.  Index cur: the frame being
+   rendered (after Render: the last frame's); 1 - cur: the frame before it */
+struct FilterState
+{
+	DevBuf<uint4> features;
+	DevBuf<float4> worldPos[2], moments[2], deltaDepth, shading;
+	DevBuf<float2> motion;
+	DevBuf<float4> filtered[2];          /* [cur]: the frame's phase-1 output (the next frame's history); [1 - cur]: phase 2's */
+	int cur = 0;
+	size_t pixels = 0;                   /* what the buffers hold (0: not allocated) */
+	bool historyValid = false;           /* the buffers of 1 - cur hold the previous frame */
+	lh2_ViewPyramid prevView{};
+	hipEvent_t ev[5] = {};               /* the chain's start, and the stop events of prepare and the three passes */
+	float ms[4] = {};                    /* the last filtered frame's kernel times (ms) */
+};
+
 struct FrameStats   /* per-frame values delivered by k_finalize into pinned host memory */
 {
 	uint32_t rayCount[LH2_MAX_BOUNCES + 1];
@@ -173,6 +191,13 @@ public:
 	void PackTile( void* devDst, bool ordered = false, void* consumer = nullptr );   /* owned rows, local order (async); ordered: with the stream consumer (null: the null stream) both ways */
 	hipEvent_t evConsumer = nullptr, evPacked = nullptr;
 	void GetFrame( float* hostOut4 );                      /* finalizeRender output: acc / samplesTaken */
+	/* the denoise mode (setting "filter"): its buffers of the last frame, to the host (LH2_FILTER_BUF_*, lh2_rendercore.h),
+	   the last frame's kernel times, and a unit entry that runs prepare (stage 0) or one a-trous pass (stage 1 .. 3) on host arrays */
+	void GetFilterBuffer( int which, void* hostOut );
+	void GetFilterTimes( float* ms4 );
+	void FilterUnit( const lh2_FilterUnit& u );
+	void SetFilterAllowed( bool on );    /* MultiDevice: a band has no neighbours across its edge, so no core of it filters */
+	bool FilterOn() const { return filterOn && filterAllowed; }
 	/* in-process multi-device gather (multidevice.cpp): rows packed by the core of rank `rank` of a
 	   band partition, already on this device, into this accumulator (async); then the frame output
 	   of the whole accumulator again (finalizeRender + display copy, no statistics) */
@@ -202,6 +227,14 @@ public:
 
 private:
 	void EnsureBuffers();
+	void EnsureFilterBuffers();
+	void RunFilter( const lh2_ViewPyramid& view );
+	bool filterOn = false, filterAllowed = true, frameFiltered = false;
+	int filterLds = -1;                  /* the a-trous passes' taps from an LDS tile (1), through L1 / L2 (0); -1: the measured pick per pass */
+	float clampDirect = LH2_FILTER_CLAMP_DIRECT, clampIndirect = LH2_FILTER_CLAMP_INDIRECT;
+	FilterState fl;
+	/* the a-trous passes' tap source per pass (1: an LDS tile), by measurement (profiles/ *_ab_filter_lds.txt) */
+	static constexpr int kFilterLdsPick[3] = { 1, 1, 1 };
 	void ConcatenateBlas( int instanceCount );
 	void BuildBlas4( CoreMeshHost& m, const float* nodes2 );
 	void FlushBuilds();
