@@ -611,13 +611,12 @@ __global__ __launch_bounds__( 256, LH2_PACKET_MINWAVES ) void k_trace_closest_pa
 /* the camera fused into the primary packet launch: each lane makes its path's primary ray (camera_path) and traces it;
    no camera launch, no ray round trip through HBM.  The launch also does the frame's counter and work-queue resets
    (cp.initC), behind the previous frame on the core stream and beside it on the ahead stream alike (RenderCore::
-   kPrimaryResets): the resets touch only this frame parity's block, and the launch's own work-queue heads (a fixed slot
+   PrimaryStage): the resets touch only this frame parity's block, and the launch's own work-queue heads (a fixed slot
    the finalize two frames back zeroes) are left alone */
 __global__ __launch_bounds__( 256, LH2_PRIMARY_MINWAVES ) void k_trace_primary_packet( const CameraParams cp, const SceneDev s,
 	const TraceArgs a, float4* T4, float4* Q4 )
 {
-	/* the frame's resets, the camera launch's (every work-queue head but the launch's own); initC is null only in an
-	   LH2_PRIMARY_RESETS=0 build, where a k_init_counters launch before this one on the ahead stream does them */
+	/* the frame's resets, the camera launch's (every work-queue head but the launch's own); Render always sets initC */
 	if (cp.initC)
 		for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < (uint32_t)max( cp.cursorWords, LH2_SEGS ); i += gridDim.x * 256u)
 			init_counters( cp.initC, cp.pathCount, cp.segStride, cp.cursors, cp.cursorWords, (int)i, cp.keepCursor );
@@ -2025,10 +2024,6 @@ __global__ __launch_bounds__( 256, LH2_SHADE_MINWAVES ) void k_shade_ref( const 
 	}
 }
 
-__global__ void k_init_counters( Counters* c, uint32_t pathCount, uint32_t segStride, uint32_t* cursors, int cursorWords, int keep )
-{
-	init_counters( c, pathCount, segStride, cursors, cursorWords, blockIdx.x * blockDim.x + threadIdx.x, keep );
-}
 /* the hand-off from bounce L to bounce L + 1 (InitCountersSubsequent, .cuda.cu:76-84): the extension
    rays counted into segNext become the next bounce's paths (the counts ping-pong, Counters::segPath),
    the retired counts of bounce L are zeroed for the shade launch of L + 1; the shadow split's snapshot;
@@ -2207,11 +2202,6 @@ template <class K> static int occupancy( K kernel )
 }
 
 extern "C" {
-void lh2_launch_init_counters( Counters* c, uint32_t pathCount, uint32_t segStride, uint32_t* cursors, int cursorWords, LaunchEvents ev, hipStream_t st,
-	int keepCursor )
-{
-	LH2_LAUNCH( k_init_counters, (cursorWords + 255) / 256 + 1, 256, st, ev, c, pathCount, segStride, cursors, cursorWords, keepCursor );
-}
 void lh2_launch_counters_next( Counters* c, const BounceAdvance* a, int pathLength, int resetShadow, LaunchEvents ev, hipStream_t st )
 {
 	LH2_LAUNCH( k_counters_next, 1, 64, st, ev, c, *a, pathLength, resetShadow );

@@ -241,7 +241,7 @@ void RenderCore::SetFilterAllowed( bool on )
    of ceil(paths / LH2_SEGS)); shadow rays: 2 per path */
 void RenderCore::EnsurePaths( uint32_t paths )
 {
-	if ((size_t)paths + 64 > ps.cap)
+	if (!PathsFit( paths ))
 	{
 		ps.cap = (size_t)paths + (paths >> 4) + 64;
 		for (int i = 0; i < 2; i++) ps.rayO[i].resize( ps.cap ), ps.rayD[i].resize( ps.cap ), ps.T4[i].resize( ps.cap ), ps.Q4[i].resize( ps.cap );
@@ -998,6 +998,40 @@ SceneDev RenderCore::MakeSceneDev()
 
 static inline uint32_t XorShift( uint32_t& s ) { s ^= s << 13; s ^= s >> 17; s ^= s << 5; return s; }  /* platform/system.cpp:48 */
 
+/* the view's camera basis: right = p2 - p1, up = p3 - p1 */
+static void SetCameraView( CameraParams& cp, const lh2_ViewPyramid& view )
+{
+	cp.pos = view.pos, cp.p1 = view.p1;
+	cp.right = { view.p2.x - view.p1.x, view.p2.y - view.p1.y, view.p2.z - view.p1.z };
+	cp.up = { view.p3.x - view.p1.x, view.p3.y - view.p1.y, view.p3.z - view.p1.z };
+}
+
+/* a frame being queued: its plan, and what Render's stages hand on to each other */
+struct Frame
+{
+	const FramePlan plan;
+	const lh2_ViewPyramid& view;
+	SceneDev sd{};
+	int tlas = 0;                        /* the TLAS slot this frame reads (evTlasFree after its finalize) */
+	FrameSlots s{};                      /* this frame's parity: its counters, work-queue heads, shadow stream and ray-count log */
+	CameraParams cp{};
+	int in = 0;                          /* the ping-pong set the bounce reads; its shade launch writes the other one */
+	int pl = 0, tailL = 0;               /* bounces launched so far; the path-tail launch, once queued */
+	bool snapped = false, sideOn = false;   /* the shadow rays before the tail: snapshot taken, traced on the side stream */
+	uint32_t* hvReadBlock = nullptr;     /* the heavy-packet block the primary packets read */
+};
+
+FrameSlots RenderCore::Slots() const
+{
+	const size_t fp = (size_t)ps.fp;
+	return { ps.counters.ptr + fp, ps.cursors.ptr + fp * LH2_CURSOR_SLOTS * LH2_CURSOR_WORDS, ps.rayLog.ptr + fp * LH2_RAYLOG,
+		ps.shO.ptr + fp * ps.shCap, ps.shD.ptr + fp * ps.shCap, ps.shP.ptr + fp * ps.shCap,
+		ps.shMask.ptr + fp * ps.shMaskWords, ps.shSnap.ptr + fp * LH2_SEGS * LH2_SEGCOUNT_STRIDE, delta.ptr + fp * scrwidth * scrheight };
+}
+
+/* a frame is six steps: the plan (every decision, no HIP call), the state transitions and buffers, then the launch stages.
+   CoreStats timings come from the stop events recorded by the launches themselves (LaunchEvents): no hipEventRecord
+   between kernels */
 void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* rendercore.cpp:463-609 */
 {
 	if (!initialized) FatalError( "Render before Init" );
@@ -1005,371 +1039,410 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 	if (geometryDirty || instancesDirty) UpdateToplevel();
 	if (!dMaterials.ptr) FatalError( "Render before SetMaterials" );
 	const auto t0 = std::chrono::high_resolution_clock::now();
-	/* CoreStats timings come from the stop events recorded by the launches themselves (LaunchEvents):
-	   no hipEventRecord between kernels */
-	const bool restart = converge == LH2_RESTART || firstConvergingFrame;
-	if (restart)
-	{
-		samplesTaken = 0;
-		firstConvergingFrame = true;
-		camRNGseed = 0x12345678;
-	}
-	if (converge == LH2_CONVERGE) firstConvergingFrame = false;
-	const int tileRows = TileRows();
-	const uint32_t pathCount = (uint32_t)tileRows * (uint32_t)scrwidth * (uint32_t)scrspp;
+	Frame f{ PlanFrame( view, converge ), view };
+	BeginFrame( f, converge );
+	PrimaryStage( f );
+	BounceLoop( f );
+	FinalShadows( f );
+	FinishFrame( f );
+	frameHostMs = std::chrono::duration<double, std::milli>( std::chrono::high_resolution_clock::now() - t0 ).count();
+}
+
+/* every decision of the frame, from the settings, the scene facts and the state that crosses frames (PathStreams); a mode
+   (the filter, PrimeRef) appears here, not in the stages */
+FramePlan RenderCore::PlanFrame( const lh2_ViewPyramid& view, int converge ) const
+{
+	FramePlan p{};
+	p.restart = converge == LH2_RESTART || firstConvergingFrame;
+	p.tileRows = TileRows();
+	p.pathCount = (uint32_t)p.tileRows * (uint32_t)scrwidth * (uint32_t)scrspp;
+	/* segmented path / ray streams (lh2_kernels.h): LH2_SEGS segments of segStride records */
+	p.segStride = (p.pathCount + LH2_SEGS - 1) / LH2_SEGS;
+	p.small = (float)p.pathCount <= kSmallFramePaths;
 	/* the denoise mode (whole frames only: a tile has no neighbours across its edge; not in PrimeRef mode): the plain
 	   wavefront loop, one launch pair per bounce behind the previous frame - no path tail, no early or terminal shade, no
 	   overlap of consecutive frames; the accumulator (two planes) holds this frame's samples only, and the lens is a pinhole */
-	const bool filt = FilterOn() && fl.pixels && tileRows == scrheight && !primeRef;
-	/* converge == Restart resets the history (the first converging frame after it restarts the accumulation too, as in the
-	   reference, but keeps the history) */
-	if (filt && converge == LH2_RESTART) fl.historyValid = false;
-	const SceneDev sd = MakeSceneDev();
-	const int frameTlas = tlasSlot;   /* the TLAS slot this frame reads (evTlasFree after its finalize) */
-	/* the accumulator reset of a restart is folded into the camera launch (each pixel's first sample zeroes
-	   it; rows outside this rank's tile stay zero from SetTarget); a changed tile clears the whole frame */
-	if (restart && tileChanged) CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * (size_t)scrwidth * scrheight, stream ) );
-	EnsurePaths( pathCount );
-	/* segmented path / ray streams (lh2_kernels.h): LH2_SEGS segments of segStride records; shadow rays in
-	   segments of shadowStride */
-	ps.count = pathCount;
-	ps.segStride = (pathCount + LH2_SEGS - 1) / LH2_SEGS;
-	ps.shadowStride = (uint32_t)(ps.shCap / LH2_SEGS);
-	ps.pl = 0, ps.tailL = 0;
-	/* this frame's parity: its counters, work-queue heads, shadow stream and ray-count log (PathStreams) */
-	ps.fp ^= 1;
-	Counters* const c = FrameCounters();
-	uint32_t* const cursors = FrameCursors();
-	uint32_t* const rayLog = FrameRayLog();
-	float4* const shO = ps.shO.ptr + (size_t)ps.fp * ps.shCap;
-	float4* const shD = ps.shD.ptr + (size_t)ps.fp * ps.shCap;
-	float4* const shP = ps.shP.ptr + (size_t)ps.fp * ps.shCap;
-	uint32_t* const shMask = ps.shMask.ptr + (size_t)ps.fp * ps.shMaskWords;
-	uint32_t* const shSnap = ps.shSnap.ptr + (size_t)ps.fp * LH2_SEGS * LH2_SEGCOUNT_STRIDE;   /* the rays queued before the tail */
-	float4* const frameDelta = delta.ptr + (size_t)ps.fp * scrwidth * scrheight;
-	/* primary rays (camera.h) for every sample of the tile; the camera launch also resets the frame's
-	   counters and work-queue heads (k_init_counters) */
-	CameraParams cp{};
-	cp.pos = view.pos, cp.p1 = view.p1;
-	cp.right = { view.p2.x - view.p1.x, view.p2.y - view.p1.y, view.p2.z - view.p1.z };
-	cp.up = { view.p3.x - view.p1.x, view.p3.y - view.p1.y, view.p3.z - view.p1.z };
-	cp.aperture = filt ? 0.0f : view.aperture, cp.distortion = view.distortion, cp.geometryEpsilon = geometryEpsilon;
-	cp.w = scrwidth, cp.h = scrheight, cp.pass = samplesTaken;
-	cp.R0 = XorShift( camRNGseed );
-	cp.y0 = std::max( 0, tileY0 ), cp.tileRows = tileRows;
-	cp.band = tileBand > 0 ? tileBand : std::max( 1, tileRows ), cp.bandStride = tileBand > 0 ? tileStride : std::max( 1, tileRows );
-	cp.tiled = tiledRays;
-	cp.primeRef = primeRef;
-	cp.initC = c, cp.cursors = cursors, cp.cursorWords = LH2_CURSOR_SLOTS * LH2_CURSOR_WORDS;
-	cp.pathCount = pathCount, cp.segStride = ps.segStride;
-	cp.clearAcc = restart && !tileChanged ? accumulator.ptr : nullptr;
-	if (filt)
-	{
-		CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * 2 * (size_t)scrwidth * scrheight, stream ) );
-		cp.clearAcc = nullptr;
-	}
+	p.filt = FilterOn() && fl.pixels && p.tileRows == scrheight && !primeRef;
+	p.aperture = p.filt ? 0.0f : view.aperture;
+	p.packets = tiledRays && UsePackets();
 	/* heavy-first primary packets: this frame reads the block the previous one recorded, and records into the
-	   other one, which the camera launch zeroes (a new layout zeroes both) */
-	ps.hvOn = packetHeavy != 0 && tiledRays && UsePackets() && !primeRef;
-	if (ps.hvOn)
+	   other one (a new layout, hvRelayout, zeroes both) */
+	p.hvOn = packetHeavy != 0 && p.packets && !primeRef;
+	p.hvCap = (p.segStride + 63) / 64;
+	p.hvRelayout = p.hvOn && p.hvCap != ps.hvCap;
+	for (int k = 0; k < LH2_SEGS; k++)
 	{
-		const uint32_t cap = (ps.segStride + 63) / 64, maskWords = (LH2_SEGS * cap + 31) / 32;
-		if (cap != ps.hvCap)
-		{
-			ps.hvCap = cap, ps.hvMaskWords = maskWords, ps.hvBlock = LH2_HV_MASK + maskWords + LH2_SEGS * cap, ps.hvParity = 0;
-			ps.hv.resize( 2 * (size_t)ps.hvBlock );
-			CHK_HIP( hipMemsetAsync( ps.hv.ptr, 0, sizeof( uint32_t ) * 2 * ps.hvBlock, stream ) );
-			ps.relaid = true;
-		}
-		cp.hvZero = ps.hv.ptr + (size_t)(1 - ps.hvParity) * ps.hvBlock, cp.hvZeroWords = LH2_HV_MASK + ps.hvMaskWords;
+		const uint32_t lo = (uint32_t)k * p.segStride, n = p.pathCount > lo ? std::min( p.pathCount - lo, p.segStride ) : 0u;
+		p.hvTiles += (n + 63) / 64;
 	}
-	const int grid = TraceGrid();
+	p.growPaths = !PathsFit( p.pathCount );
+	p.traceGrid = TraceGrid();
 	/* the shade launches walk their segment with a static block stride: blocks beyond the resident ones start as others
 	   end, so more, smaller block shares balance the launch's end.  shadeBlocks 0: about shadePathsPerThread paths per
 	   thread, between the trace grid and shadeMaxBlocks per CU (the N = 8 share 12 per CU, config 3 24: -1.5 / -1.5 %,
 	   profiles/r04al_ab.txt, r04am_ab.txt) */
-	const int shadeGrid = shadeBlocks > 0 ? smCount * shadeBlocks : std::max( grid, std::min( smCount * kShadeMaxBlocks,
-		(int)((double)pathCount / (256.0 * kShadePathsPerThread)) ) );
+	p.shadeGrid = shadeBlocks > 0 ? smCount * shadeBlocks : std::max( p.traceGrid, std::min( smCount * kShadeMaxBlocks,
+		(int)((double)p.pathCount / (256.0 * kShadePathsPerThread)) ) );
 	/* the camera fused into the primary packet launch: the heavy-packet block it records into must be zero (the previous
 	   fused frame's first shade launch zeroed it) */
-	const bool fusedCam = cameraFused && tiledRays && UsePackets() && !primeRef;
+	p.fusedCam = cameraFused && p.packets && !primeRef;
 	/* round 6: a frame whose primary rays are traced per ray (no packets: a scene beyond the Infinity Cache,
 	   config 5) takes the same frame overlap.  Its camera launch (with the frame's resets) and its per-ray primary launch
 	   write the frame parity's primary buffers on the ahead stream, the primary launch with a global stack of its own
 	   (PathStreams::aheadStack: the previous frame's bounce launch still uses gstack) */
-	const bool camAhead = kCamAhead && !fusedCam && cameraFused && !primeRef && TraceVersion() == 7;
-	const bool pFrame = fusedCam || camAhead;   /* the frame's primary stage may run beside the previous frame */
+	p.camAhead = kCamAhead && !p.fusedCam && cameraFused && !primeRef && TraceVersion() == 7;
+	p.pFrame = p.fusedCam || p.camAhead;   /* the frame's primary stage may run beside the previous frame */
 	/* the primary stage beside the previous frame (frame overlap), or behind it on the core stream: on a restart (the
-	   launch zeroes accumulator pixels), after a change of scene data, buffers or tile, or when the previous frame had no
-	   such primary stage */
-	const bool serialize = filt || !frameOverlap || !ps.lastFused || ps.relaid || tileChanged || sceneVersion != ps.lastSceneVersion;
-	/* a restart beside the previous frame: the accumulator is zeroed on the core stream, behind the previous frame's finalize
-	   and before this frame's first addition there (the early shade adds into the delta), not by the primary launch */
-	if (pFrame && !serialize && cp.clearAcc)
-	{
-		CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * (size_t)scrwidth * scrheight, stream ) );
-		cp.clearAcc = nullptr;
-	}
-	hipStream_t primStream = stream;
-	/* the primary launch's work-queue heads: slot 1 of the frame parity's block, zeroed by the finalize of the frame before
-	   the previous one (FrameStatsDev::zeroHeads) */
-	const uint32_t primSlot = 1u;
-	cp.keepCursor = -1;   /* a camera launch behind the previous frame resets every work-queue head */
-	if (pFrame)
-	{
-		/* beside the previous frame (on the ahead stream, after the previous frame's shade launch before its path tail, or
-		   its first without one: the last reader of the primary buffers and of the heavy-packet block this frame records
-		   into) or behind it (core stream), the primary launch does the frame's resets itself (kPrimaryResets: this frame
-		   parity's counters and heads, whose last user, the frame before the previous one, is done); only an
-		   LH2_PRIMARY_RESETS=0 build queues a k_init_counters launch before it on the ahead stream instead.  Its own
-		   work-queue heads (slot primSlot, zeroed by the finalize two frames back) are left alone */
-		primStream = serialize ? stream : aheadStream;
-		cp.keepCursor = (int)(primSlot * LH2_CURSOR_WORDS);
-		if (serialize) cp.initC = c;
-		else
-		{
-			CHK_HIP( hipStreamWaitEvent( aheadStream, ps.overlapEv, 0 ) );
-			if (kPrimaryResets) cp.initC = c;   /* the primary launch resets them itself: no launch (and its gap) before it */
-			else
-			{
-				lh2_launch_init_counters( c, pathCount, ps.segStride, cursors, LH2_CURSOR_SLOTS * LH2_CURSOR_WORDS, {}, aheadStream, -LH2_CURSOR_WORDS );
-				cp.initC = nullptr;
-			}
-		}
-		if (ps.hvOn && !ps.hvNextZeroed) CHK_HIP( hipMemsetAsync( cp.hvZero, 0, sizeof( uint32_t ) * cp.hvZeroWords, primStream ) );
-		cp.hvZero = nullptr, cp.hvZeroWords = 0;
-		ps.relaid = false;
-	}
-	ps.hvNextZeroed = false;
-	uint32_t* hvReadBlock = nullptr;
-	int maxPL = primeRef ? LH2_MAX_BOUNCES : maxPathLength;
+	   launch zeroes accumulator pixels), after a change of scene data, buffers (BeginFrame is about to grow them) or tile,
+	   or when the previous frame had no such primary stage */
+	const bool relaid = ps.relaid || p.growPaths || p.hvRelayout;
+	p.serialize = p.filt || !frameOverlap || !ps.lastFused || relaid || tileChanged || sceneVersion != ps.lastSceneVersion;
+	/* the accumulator reset of a restart is folded into the camera launch (each pixel's first sample zeroes it; rows outside
+	   this rank's tile stay zero from SetTarget); a changed tile clears the whole frame.  A restart beside the previous
+	   frame: the accumulator is zeroed on the core stream, behind the previous frame's finalize and before this frame's
+	   first addition there (the early shade adds into the delta), not by the primary launch */
+	p.clearAll = p.restart && tileChanged;
+	p.clearBehind = p.restart && !tileChanged && !p.filt && p.pFrame && !p.serialize;
+	p.clearByLaunch = p.restart && !tileChanged && !p.filt && !p.clearBehind;
+	p.maxPL = primeRef ? LH2_MAX_BOUNCES : maxPathLength;
 	/* no specular event and no alpha cut-out in any material: every path ends at its second vertex,
 	   so the bounce after it would be empty; not launching it saves three launches (~25 us) */
-	if (!primeRef && diffuseOnly) maxPL = std::min( maxPL, 2 );
+	if (!primeRef && diffuseOnly) p.maxPL = std::min( p.maxPL, 2 );
 	/* the path tail (setting "pathTail"): bounces pathTail .. maxPL in one launch of k_trace_path4d */
-	const int tailL = (!primeRef && !filt && pathTail >= 2 && pathTail <= maxPL && TraceVersion() == 7) ? pathTail : 0;
+	p.tailL = (!primeRef && !p.filt && pathTail >= 2 && pathTail <= p.maxPL && TraceVersion() == 7) ? pathTail : 0;
 	/* early shade: the first shade launch follows the primary launch on the ahead stream and writes the ping-pong buffer
 	   the previous frame's launches after its overlap event do not use (PathStreams::busy / earlyOk).  Only when this
 	   frame has a path tail from bounce 3 on: else its first shade launch is its overlap event (and, with the tail from
 	   bounce 2, its shadow snapshot), and on the ahead stream neither would follow the previous frame's finalize (the
 	   side shadow launch and the next frames' early shades would add into the accumulator and the delta before the
 	   previous frame is finalized) */
-	const bool early = pFrame && !serialize && earlyShade && frameOverlap == 1 && ps.earlyOk && (float)pathCount <= kSmallFramePaths &&
-		tailL >= 3;
-	ps.early = early;
-	ps.in = early ? ps.busy : 0;
+	p.early = p.pFrame && !p.serialize && earlyShade && frameOverlap == 1 && ps.earlyOk && p.small && p.tailL >= 3;
+	/* without lights no path samples one (RandomPointOnLight: lightPdf 0), so there are no shadow
+	   rays and their launches are not queued */
+	p.shadows = nArea + nPoint + nSpot + nDir > 0;
+	/* shadow overlap: the shade launch before the tail snapshots the queued shadow rays (advance_bounce), and the side
+	   launch traces them beside the tail */
+	p.overlap = p.shadows && p.tailL && shadowOverlap;
+	/* RenderCore_PrimeRef traces the shadow rays of every bounce right after it, and hands off to the next bounce in a
+	   launch of its own after that (their counts are reset first); else one shadow launch ends the frame */
+	p.bounceShadows = primeRef && p.shadows, p.finalShadows = !primeRef && p.shadows, p.handOffLaunch = primeRef;
+	p.terminal = !primeRef && !p.filt && !p.shadows && !canEmit && terminalShade;
+	p.hvFactor = packetHeavy > 0 ? packetHeavy : p.tailL ? 3.0f : 2.0f;
+	/* the next frame's primary launch starts after this frame's first shade launch (the last reader of the primary
+	   buffers), or (frameOverlap 1) after the shade launch before the path tail: beside the latency-bound tail */
+	p.overlapL = frameOverlap == 1 && p.tailL ? p.tailL - 1 : 1;
+	/* a bounce launch the next frame's primary launch will likely run beside (this frame overlapped: the next one
+	   probably does too): fewer blocks per CU, so the packets' latency-bound waves get slots from the start instead
+	   of the bounce launch's tail (config 2: 4262-4296 -> 4437-4442 Mrays/s at 5, r03q_ab_trace_blocks.txt), and the
+	   7-wave variant (8 waves slow the packets beside the launch, r04ad) */
+	p.besideNext = !p.serialize && p.fusedCam;
+	p.besideGrid = smCount * std::min( blocksPerCU, kOverlapTraceBlocks );
+	/* traceWaves 0: the 7-wave variant for every scene (round 6: instanced scenes too, with the early node loads), on its occupancy's grid */
+	p.traceWaves = ScenePicksWaves();
+	p.closestGrid = smCount * ClosestBlocksPerCU( p.traceWaves );
+	p.primaryGrid = p.packets ? PacketGrid() : p.closestGrid;
+	/* the path tail's kernel variant (pathTailWaves 0): 4 waves per SIMD (128 VGPRs) for every frame since the shade batches write their
+	   shadow rays at once (its spills 68 -> 40 VGPRs; small frames: config 3 -0.8 %, profiles/r06s_ab_tail_waves.txt); 3
+	   (no spills) was the small frames' variant before */
+	p.tailWaves = pathTailWaves == 3 || pathTailWaves == 4 ? (uint32_t)pathTailWaves : 4u;
+	/* with the overlap the path tail runs fewer blocks per CU and leaves registers for the side launch's waves
+	   (pathTailBlocks; 0: 3 for small frames, whose tail phase is the frame's longest, else 2) */
+	const int occ = p.tailWaves == 4 ? pathBlocksPerCU4 : pathBlocksPerCU;
+	const int ptBlocks = pathTailBlocks > 0 ? pathTailBlocks : p.overlap ? (p.small ? 3 : 2) : occ;
+	p.tailGrid = smCount * std::min( std::min( blocksPerCU, occ ), ptBlocks );
+	/* the global stacks (sideStack, gstack) are sized for maxBlocksPerCU blocks per CU: the shadow grids stay within it */
+	const int sb = sideBlocks >= 0 ? sideBlocks : p.small ? 3 : 4;
+	p.sideGrid = sb > 0 ? smCount * std::min( sb, maxBlocksPerCU ) : p.traceGrid;
+	p.finalShadowGrid = finalShadowBlocks > 0 ? smCount * std::min( finalShadowBlocks, maxBlocksPerCU ) : p.traceGrid;
+	return p;
+}
+
+/* the frame's state transitions and buffers; `f` gets the scene and the frame parity's slots */
+void RenderCore::BeginFrame( Frame& f, int converge )
+{
+	const FramePlan& p = f.plan;
+	if (p.restart)
+	{
+		samplesTaken = 0;
+		firstConvergingFrame = true;
+		camRNGseed = 0x12345678;
+	}
+	if (converge == LH2_CONVERGE) firstConvergingFrame = false;
+	/* converge == Restart resets the history (the first converging frame after it restarts the accumulation too, as in the
+	   reference, but keeps the history) */
+	if (p.filt && converge == LH2_RESTART) fl.historyValid = false;
+	f.sd = MakeSceneDev();
+	f.tlas = tlasSlot;
+	if (p.clearAll) CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * (size_t)scrwidth * scrheight, stream ) );
+	EnsurePaths( p.pathCount );
+	/* shadow rays in segments of shadowStride */
+	ps.count = p.pathCount, ps.segStride = p.segStride, ps.shadowStride = (uint32_t)(ps.shCap / LH2_SEGS);
+	ps.fp ^= 1;
+	f.s = Slots();
+	if (p.filt) CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * 2 * (size_t)scrwidth * scrheight, stream ) );
+	if (p.hvRelayout)
+	{
+		ps.hvCap = p.hvCap, ps.hvMaskWords = (LH2_SEGS * p.hvCap + 31) / 32;
+		ps.hvBlock = LH2_HV_MASK + ps.hvMaskWords + LH2_SEGS * p.hvCap, ps.hvParity = 0;
+		ps.hv.resize( 2 * (size_t)ps.hvBlock );
+		CHK_HIP( hipMemsetAsync( ps.hv.ptr, 0, sizeof( uint32_t ) * 2 * ps.hvBlock, stream ) );
+		ps.relaid = true;
+	}
+	if (p.clearBehind) CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * (size_t)scrwidth * scrheight, stream ) );
+}
+
+/* the closest-hit launch of bounce `pathLength` over the rays of `rays`: the bounce's paths (the path counts ping-pong,
+   Counters::segPath) and its work-queue heads (the primary launch's: kPrimarySlot) */
+TraceArgs RenderCore::BounceArgs( const Frame& f, int pathLength, const PathSet& rays ) const
+{
+	TraceArgs ta{};
+	ta.version = TraceVersion();
+	rays.Rays( ta );
+	ta.segCounts = f.s.c->segPath[(pathLength - 1) & 1], ta.segStride = f.plan.segStride, ta.segBack = f.s.c->segBack[(pathLength - 1) & 1];
+	ta.cursor = f.s.Cursor( pathLength );
+	ta.refill = (uint32_t)refillOther, ta.leafBatch = (uint32_t)leafBatch;
+	ta.gstack = ps.gstack.ptr;
+	return ta;
+}
+
+/* what the shade launch of a bounce and the path tail share */
+ShadeParams RenderCore::ShadeArgs( const Frame& f, int pathLength ) const
+{
+	ShadeParams sp{};
+	sp.shadowStride = ps.shadowStride;
+	sp.shO = f.s.shO, sp.shD = f.s.shD, sp.shP = f.s.shP;
+	sp.acc = accumulator.ptr, sp.counters = f.s.c;
+	sp.w = scrwidth, sp.h = scrheight, sp.pass = samplesTaken, sp.pathLength = pathLength, sp.maxPathLength = f.plan.maxPL;
+	sp.probePixel = probeX + scrwidth * probeY;
+	sp.spreadAngle = f.view.spreadAngle;
+	if (f.plan.filt)
+	{
+		sp.fFeatures = fl.features.ptr, sp.fWorldPos = fl.worldPos[fl.cur].ptr, sp.fDeltaDepth = fl.deltaDepth.ptr;
+		sp.fPos = f.cp.pos, sp.fP1 = f.cp.p1, sp.fRight = f.cp.right, sp.fUp = f.cp.up;
+	}
+	return sp;
+}
+
+/* the hand-off from bounce `pathLength` to the next one; before the path tail it also takes the shadow overlap's snapshot */
+BounceAdvance RenderCore::HandOff( const Frame& f, int pathLength ) const
+{
+	Counters* const c = f.s.c;
+	const int cur = (pathLength - 1) & 1, next = pathLength & 1;
+	const bool beforeTail = pathLength + 1 == f.plan.tailL, snap = f.plan.overlap && beforeTail;
+	return { c->segPath[next], c->segBack[next], c->segPath[cur], c->segBack[cur], f.s.rayLog, ps.activeLog, beforeTail,
+		snap ? f.s.shSnap : nullptr, snap ? f.s.Cursor( LH2_SHADOW_SLOT ) : nullptr };
+}
+
+/* a shadow launch with fused finalizeConnections (rendercore.cpp:575-592) over this frame's shadow stream */
+TraceArgs RenderCore::ShadowArgs( const FrameSlots& s, const uint32_t* segCounts, int cursorSlot, int leafBatch, int* gstack ) const
+{
+	TraceArgs ta{};
+	ta.version = TraceVersion();
+	ta.rayO = s.shO, ta.rayD = s.shD, ta.segCounts = segCounts, ta.segStride = ps.shadowStride;
+	ta.cursor = s.Cursor( cursorSlot );
+	ta.refill = (uint32_t)refillOther, ta.leafBatch = (uint32_t)leafBatch;
+	ta.mask = s.shMask, ta.potentials = s.shP, ta.acc = accumulator.ptr, ta.gstack = gstack;
+	return ta;
+}
+
+void RenderCore::LaunchClosest( const Frame& f, const TraceArgs& ta, int grid, int pathLength, hipStream_t st )
+{
+#ifdef LH2_TOUCH
+	TouchBegin();
+#endif
+	lh2_launch_trace_closest( &f.sd, &ta, grid, { nullptr, ps.evTrace[pathLength] }, st );
+#ifdef LH2_TOUCH
+	TouchReport( pathLength );
+#endif
+}
+
+/* primary rays (camera.h) for every sample of the tile, and their trace launch: the camera fused into the primary packet
+   launch, or a camera launch and a closest-hit launch (packets or per ray) */
+void RenderCore::PrimaryStage( Frame& f )
+{
+	const FramePlan& p = f.plan;
+	CameraParams& cp = f.cp;
+	SetCameraView( cp, f.view );
+	cp.aperture = p.aperture, cp.distortion = f.view.distortion, cp.geometryEpsilon = geometryEpsilon;
+	cp.w = scrwidth, cp.h = scrheight, cp.pass = samplesTaken;
+	cp.R0 = XorShift( camRNGseed );
+	cp.y0 = std::max( 0, tileY0 ), cp.tileRows = p.tileRows;
+	cp.band = tileBand > 0 ? tileBand : std::max( 1, p.tileRows ), cp.bandStride = tileBand > 0 ? tileStride : std::max( 1, p.tileRows );
+	cp.tiled = tiledRays;
+	cp.primeRef = primeRef;
+	/* the camera launch (or the fused primary launch) also resets the frame's counters and work-queue heads */
+	cp.initC = f.s.c, cp.cursors = f.s.cursors, cp.cursorWords = LH2_CURSOR_SLOTS * LH2_CURSOR_WORDS;
+	cp.pathCount = p.pathCount, cp.segStride = p.segStride;
+	cp.clearAcc = p.clearByLaunch ? accumulator.ptr : nullptr;
+	/* heavy-first primary packets: the block the previous frame recorded, and the other one, which the camera launch zeroes */
+	uint32_t *hvRead = nullptr, *hvWrite = nullptr;
+	if (p.hvOn)
+	{
+		hvRead = ps.hv.ptr + (size_t)ps.hvParity * ps.hvBlock, hvWrite = ps.hv.ptr + (size_t)(1 - ps.hvParity) * ps.hvBlock;
+		cp.hvZero = hvWrite, cp.hvZeroWords = LH2_HV_MASK + ps.hvMaskWords;
+		ps.hvParity = 1 - ps.hvParity;
+	}
+	hipStream_t primStream = stream;
+	cp.keepCursor = -1;   /* a camera launch behind the previous frame resets every work-queue head */
+	if (p.pFrame)
+	{
+		/* beside the previous frame (on the ahead stream, after the previous frame's shade launch before its path tail, or
+		   its first without one: the last reader of the primary buffers and of the heavy-packet block this frame records
+		   into) or behind it (core stream), the primary stage does the frame's resets itself (this frame parity's counters
+		   and heads, whose last user, the frame before the previous one, is done: no launch, and its gap, before it;
+		   profiles/r05f_ab_primary_resets.txt).  Its own work-queue heads (kPrimarySlot) are left alone */
+		primStream = p.serialize ? stream : aheadStream;
+		cp.keepCursor = kPrimarySlot * LH2_CURSOR_WORDS;
+		if (!p.serialize) CHK_HIP( hipStreamWaitEvent( aheadStream, ps.overlapEv, 0 ) );
+		if (p.hvOn && !ps.hvNextZeroed) CHK_HIP( hipMemsetAsync( cp.hvZero, 0, sizeof( uint32_t ) * cp.hvZeroWords, primStream ) );
+		cp.hvZero = nullptr, cp.hvZeroWords = 0;
+		ps.relaid = false;
+	}
+	ps.hvNextZeroed = false;
+	f.in = p.early ? ps.busy : 0;
 	ps.earlyOk = false;
 	/* the frame's start: a marker before the camera launch (~4 us of idle GPU), not the launch's own start
 	   event (hipExtLaunchKernelGGL start events cost ~8 us: tools/launch_gap.hip, profiles/r02q_launch_gap.txt) */
-	CHK_HIP( hipEventRecord( evFrame[0], pFrame ? primStream : stream ) );
-	if (fusedCam) ps.prevStop = evFrame[0];
-	else if (camAhead)
+	CHK_HIP( hipEventRecord( evFrame[0], primStream ) );
+	/* a frame whose primary stage may run beside the previous frame keeps its primary rays apart from the bounce ping-pong */
+	const PathSet prim = p.pFrame ? ps.Primary( ps.fp ) : ps.Bounce( f.in );
+	if (p.fusedCam) ps.prevStop = evFrame[0];
+	else
 	{
-		lh2_launch_camera( &cp, dBlueNoise.ptr, ps.rayOP[ps.fp].ptr, ps.rayDP[ps.fp].ptr, ps.T4P[ps.fp].ptr, ps.Q4P[ps.fp].ptr, (int)pathCount,
-			{ nullptr, ps.evCamera }, primStream );
+		lh2_launch_camera( &cp, dBlueNoise.ptr, prim.O, prim.D, prim.T4, prim.Q4, (int)p.pathCount, { nullptr, ps.evCamera }, primStream );
 		ps.prevStop = ps.evCamera;
+	}
+	if (p.restart) tileChanged = false;
+	TraceArgs ta = BounceArgs( f, 1, prim );
+	ta.packet = p.packets;
+	if (p.hvOn)
+	{
+		ta.hvRead = f.hvReadBlock = hvRead, ta.hvWrite = hvWrite;
+		ta.hvCap = ps.hvCap, ta.hvMaskWords = ps.hvMaskWords, ta.hvFactor = p.hvFactor, ta.hvTiles = p.hvTiles;
+	}
+	if (p.fusedCam)
+	{
+		/* the paths are dense (camera order): fixed counts, no segment counters */
+		ta.segCounts = nullptr, ta.segBack = nullptr, ta.countFixed = p.pathCount;
+		lh2_launch_trace_primary( &f.sd, &ta, &cp, prim.T4, prim.Q4, PacketGrid(), { nullptr, ps.evTrace[1] }, primStream );
 	}
 	else
 	{
-		lh2_launch_camera( &cp, dBlueNoise.ptr, ps.rayO[0].ptr, ps.rayD[0].ptr, ps.T4[0].ptr, ps.Q4[0].ptr, (int)pathCount, { nullptr, ps.evCamera }, stream );
-		ps.prevStop = ps.evCamera;
+		/* after its camera launch (the camera's resets set the dense segment counts); beside the previous frame it walks
+		   with a global stack of its own */
+		ta.traceWaves = (uint32_t)p.traceWaves;
+		if (primStream != stream) ta.gstack = ps.aheadStack.ptr;
+		LaunchClosest( f, ta, p.primaryGrid, 1, primStream );
 	}
-	if (restart) tileChanged = false;
-	/* without lights no path samples one (RandomPointOnLight: lightPdf 0), so there are no shadow
-	   rays and their launches are not queued */
-	const bool shadows = nArea + nPoint + nSpot + nDir > 0;
-	frameShadows = shadows;
-	/* shadow overlap: the shade launch before the tail snapshots the queued shadow rays (advance_bounce) */
-	const bool overlap = shadows && tailL && shadowOverlap;
-	bool snapped = false;
-	bool besideNext = false;   /* the next frame's primary launch may run beside the launches from here on */
-	ps.sideOn = false;
-	/* the bounce loop */
-	for (int pathLength = 1; pathLength <= maxPL; pathLength++)
-	{
-		ps.pl = pathLength;
-		/* the path counts ping-pong (Counters::segPath): this bounce's paths, and its extension rays */
-		uint32_t* const segIn = c->segPath[(pathLength - 1) & 1];
-		uint32_t* const segNext = c->segPath[pathLength & 1];
-		uint32_t* const segInBack = c->segBack[(pathLength - 1) & 1];
-		uint32_t* const segNextBack = c->segBack[pathLength & 1];
-		const bool primary = pathLength == 1 && tiledRays;
-		TraceArgs ta{};
-		ta.version = TraceVersion();
-		ta.rayO = ps.rayO[ps.in].ptr, ta.rayD = ps.rayD[ps.in].ptr, ta.segCounts = segIn, ta.segStride = ps.segStride, ta.segBack = segInBack;
-		ta.cursor = cursors + (size_t)(pathLength == 1 ? primSlot : (uint32_t)pathLength) * LH2_CURSOR_WORDS;
-		ta.refill = (uint32_t)refillOther;
-		ta.packet = primary && UsePackets() ? 1 : 0;
-		ta.leafBatch = (uint32_t)leafBatch;
-		ta.hits = ps.hits.ptr, ta.gstack = ps.gstack.ptr;
-		const bool fusedPrimary = pathLength == 1 && pFrame;   /* the primary buffers (PathStreams::rayOP ..) */
-		if (fusedPrimary) ta.rayO = ps.rayOP[ps.fp].ptr, ta.rayD = ps.rayDP[ps.fp].ptr, ta.hits = ps.hitsP[ps.fp].ptr;
-		if (pathLength == 1 && ta.packet && ps.hvOn)
-		{
-			ta.hvRead = ps.hv.ptr + (size_t)ps.hvParity * ps.hvBlock, ta.hvWrite = ps.hv.ptr + (size_t)(1 - ps.hvParity) * ps.hvBlock;
-			ta.hvCap = ps.hvCap, ta.hvMaskWords = ps.hvMaskWords, ta.hvFactor = packetHeavy > 0 ? packetHeavy : tailL ? 3.0f : 2.0f;
-			hvReadBlock = (uint32_t*)ta.hvRead;
-			ta.hvTiles = 0;
-			for (int k = 0; k < LH2_SEGS; k++)
-			{
-				const uint32_t lo = (uint32_t)k * ps.segStride, n = ps.count > lo ? std::min( ps.count - lo, ps.segStride ) : 0u;
-				ta.hvTiles += (n + 63) / 64;
-			}
-			ps.hvParity = 1 - ps.hvParity;
-		}
-		ShadeParams sp{};
-		sp.shadowStride = ps.shadowStride;
-		sp.shO = shO, sp.shD = shD, sp.shP = shP;
-		sp.acc = accumulator.ptr, sp.counters = c;
-		sp.w = scrwidth, sp.h = scrheight, sp.pass = samplesTaken, sp.pathLength = pathLength, sp.maxPathLength = maxPL;
-		sp.probePixel = probeX + scrwidth * probeY;
-		sp.spreadAngle = view.spreadAngle;
-		if (filt)
-		{
-			sp.fFeatures = fl.features.ptr, sp.fWorldPos = fl.worldPos[fl.cur].ptr, sp.fDeltaDepth = fl.deltaDepth.ptr;
-			sp.fPos = cp.pos, sp.fP1 = cp.p1, sp.fRight = cp.right, sp.fUp = cp.up;
-		}
-		if (pathLength == tailL)
-		{
-			/* the path tail: trace and shade every remaining bounce in one launch; each path's records are
-			   updated in place, its shadow rays queued for the shadow launch, and rayLog counted */
-			sp.rayO = ps.rayO[ps.in].ptr, sp.rayD = ps.rayD[ps.in].ptr, sp.T4 = ps.T4[ps.in].ptr, sp.Q4 = ps.Q4[ps.in].ptr;
-			sp.rayOut = ps.rayO[ps.in].ptr, sp.rayDOut = ps.rayD[ps.in].ptr, sp.T4Out = ps.T4[ps.in].ptr, sp.Q4Out = ps.Q4[ps.in].ptr;
-			sp.adv.rayCountLog = rayLog;
-			ta.shadeBatch = (uint32_t)pathTailBatch;
-			/* with the overlap the path tail runs fewer blocks per CU and leaves registers for the side launch's waves
-			   (pathTailBlocks; 0: 3 for small frames, whose tail phase is the frame's longest, else 2) */
-			const bool side = overlap && snapped;
-			const bool small = (float)pathCount <= kSmallFramePaths;
-			/* the kernel variant (pathTailWaves 0): 4 waves per SIMD (128 VGPRs) for every frame since the shade batches write their
-			   shadow rays at once (its spills 68 -> 40 VGPRs; small frames: config 3 -0.8 %, profiles/r06s_ab_tail_waves.txt); 3
-			   (no spills) was the small frames' variant before */
-			ta.tailWaves = pathTailWaves == 3 || pathTailWaves == 4 ? (uint32_t)pathTailWaves : 4u;
-			const int occ = ta.tailWaves == 4 ? pathBlocksPerCU4 : pathBlocksPerCU;
-			const int ptBlocks = pathTailBlocks > 0 ? pathTailBlocks : side ? (small ? 3 : 2) : occ;
-			lh2_launch_trace_path( &sd, &ta, &sp, smCount * std::min( std::min( blocksPerCU, occ ), ptBlocks ), { nullptr, ps.evTrace[pathLength] }, stream );
-			if (side)
-			{
-				/* the shadow rays of the bounces before the tail, beside it on the side stream (segment counts:
-				   the snapshot; the final launch's work-queue heads start behind them) */
-				CHK_HIP( hipStreamWaitEvent( sideStream, ps.prevStop, 0 ) );
-				TraceArgs ts{};
-				ts.version = TraceVersion();
-				ts.rayO = shO, ts.rayD = shD, ts.segCounts = shSnap, ts.segStride = ps.shadowStride;
-				ts.cursor = cursors + (size_t)(LH2_SHADOW_SLOT + 1) * LH2_CURSOR_WORDS;
-				ts.refill = (uint32_t)refillOther, ts.leafBatch = (uint32_t)kShadowLeafBatch;
-				ts.mask = shMask, ts.potentials = shP, ts.acc = accumulator.ptr, ts.gstack = ps.sideStack.ptr;
-				/* the global stack (sideStack) is sized for maxBlocksPerCU blocks per CU: the grid stays within it */
-				const int sb = sideBlocks >= 0 ? sideBlocks : small ? 3 : 4;
-				lh2_launch_trace_any( &sd, &ts, sb > 0 ? smCount * std::min( sb, maxBlocksPerCU ) : grid, 1, { nullptr, ps.evSide }, sideStream );
-				ps.fromSide = ps.prevStop;
-				ps.sideOn = true;
-			}
-			ps.fromTrace[pathLength] = ps.prevStop, ps.prevStop = ps.evTrace[pathLength];
-			ps.tailL = pathLength;   /* no shade interval of its own (Synchronize) */
-			break;
-		}
-		if (fusedPrimary && camAhead)
-		{
-			/* the per-ray primary launch after its camera launch (the camera's resets set the dense segment counts); beside the
-			   previous frame it walks with a global stack of its own; the core stream waits for it */
-			const int waves = traceWaves ? traceWaves : 7;
-			ta.traceWaves = (uint32_t)waves;
-			if (primStream != stream) ta.gstack = ps.aheadStack.ptr;
-			lh2_launch_trace_closest( &sd, &ta, smCount * ClosestBlocksPerCU( waves ), { nullptr, ps.evTrace[pathLength] }, primStream );
-			if (primStream != stream && !early) CHK_HIP( hipStreamWaitEvent( stream, ps.evTrace[pathLength], 0 ) );
-		}
-		else if (fusedPrimary)
-		{
-			/* the paths are dense (camera order): fixed counts, no segment counters; the core stream waits for it */
-			ta.segCounts = nullptr, ta.segBack = nullptr, ta.countFixed = pathCount;
-			lh2_launch_trace_primary( &sd, &ta, &cp, ps.T4P[ps.fp].ptr, ps.Q4P[ps.fp].ptr, PacketGrid(), { nullptr, ps.evTrace[pathLength] }, primStream );
-			if (primStream != stream && !early) CHK_HIP( hipStreamWaitEvent( stream, ps.evTrace[pathLength], 0 ) );
-		}
-		else
-		{
-			/* a bounce launch the next frame's primary launch will likely run beside (this frame overlapped: the next one
-			   probably does too): fewer blocks per CU, so the packets' latency-bound waves get slots from the start instead
-			   of the bounce launch's tail (config 2: 4262-4296 -> 4437-4442 Mrays/s at 5, r03q_ab_trace_blocks.txt) */
-			const bool beside = besideNext && !ta.packet;
-			/* traceWaves 0: the 7-wave variant for every scene (round 6: instanced scenes too, with the early node loads), on its occupancy's grid */
-			const int waves = traceWaves ? traceWaves : 7;
-			const int g = ta.packet ? PacketGrid() : beside ? smCount * std::min( blocksPerCU, kOverlapTraceBlocks ) : smCount * ClosestBlocksPerCU( waves );
-			ta.traceWaves = beside ? 7u : (uint32_t)waves;   /* 8 waves slow the packets beside the launch (r04ad) */
-#ifdef LH2_TOUCH
-			TouchBegin();
-#endif
-			lh2_launch_trace_closest( &sd, &ta, g, { nullptr, ps.evTrace[pathLength] }, stream );
-#ifdef LH2_TOUCH
-			TouchReport( pathLength );
-#endif
-		}
-		ps.fromTrace[pathLength] = ps.prevStop, ps.prevStop = ps.evTrace[pathLength];
-		sp.segCounts = segIn, sp.segOut = segNext, sp.segStride = ps.segStride;
-		sp.segBack = segInBack, sp.segOutBack = segNextBack;
-		/* two-ended path segments: rays with a chord through the scene box below chordSplit x its largest
-		   extent go last (setting "chordSplit"; 0: off) */
-		{
-			const float ext = std::max( std::max( sceneHi[0] - sceneLo[0], sceneHi[1] - sceneLo[1] ), sceneHi[2] - sceneLo[2] );
-			for (int k = 0; k < 3; k++) sp.chordLo[k] = sceneLo[k], sp.chordHi[k] = sceneHi[k];
-			sp.chordCut = ext > 0 ? chordSplit * ext : 0.0f;
-		}
-		/* the hand-off to the next bounce: the shade launch's last block (no launch of its own), except
-		   in PrimeRef mode, where the bounce's shadow rays are traced (and their counts reset) first */
-		const bool snap = overlap && pathLength + 1 == tailL;
-		const BounceAdvance adv{ segNext, segNextBack, segIn, segInBack, rayLog, ps.activeLog, pathLength + 1 == tailL,
-			snap ? shSnap : nullptr, snap ? cursors + (size_t)LH2_SHADOW_SLOT * LH2_CURSOR_WORDS : nullptr };
-		snapped = snapped || snap;
-		sp.advance = pathLength < maxPL && !primeRef;
-		sp.adv = adv;
-		sp.rayO = ps.rayO[ps.in].ptr, sp.rayD = ps.rayD[ps.in].ptr, sp.T4 = ps.T4[ps.in].ptr, sp.Q4 = ps.Q4[ps.in].ptr, sp.hits = ps.hits.ptr;
-		if (fusedPrimary) sp.rayO = ps.rayOP[ps.fp].ptr, sp.rayD = ps.rayDP[ps.fp].ptr, sp.T4 = ps.T4P[ps.fp].ptr, sp.Q4 = ps.Q4P[ps.fp].ptr, sp.hits = ps.hitsP[ps.fp].ptr;
-		sp.rayOut = ps.rayO[1 - ps.in].ptr, sp.rayDOut = ps.rayD[1 - ps.in].ptr, sp.T4Out = ps.T4[1 - ps.in].ptr, sp.Q4Out = ps.Q4[1 - ps.in].ptr;
-		sp.primeRef = primeRef;
-		sp.terminal = !primeRef && !filt && !shadows && !canEmit && pathLength > 1 && terminalShade;
-		sp.R0 = (uint32_t)samplesTaken * 7907u + (uint32_t)pathLength * 91771u;
-		if (pathLength == 1 && fusedCam && hvReadBlock)
-		{
-			/* the block this frame's packets read is the one the next frame records into */
-			sp.hvZero = hvReadBlock, sp.hvZeroWords = LH2_HV_MASK + ps.hvMaskWords;
-			ps.hvNextZeroed = true;
-		}
-		const bool earlyHere = early && pathLength == 1;
-		if (earlyHere) sp.acc = frameDelta;   /* the previous frame's finalize may not have read the accumulator yet */
-		lh2_launch_shade( &sd, &sp, shadeGrid, { nullptr, ps.evShade[pathLength] }, earlyHere ? aheadStream : stream );
-		if (earlyHere) CHK_HIP( hipStreamWaitEvent( stream, ps.evShade[pathLength], 0 ) );
-		ps.fromShade[pathLength] = ps.prevStop, ps.prevStop = ps.evShade[pathLength];
-		/* the next frame's primary launch starts after this frame's first shade launch (the last reader of the primary
-		   buffers), or (frameOverlap 1) after the shade launch before the path tail: beside the latency-bound tail */
-		if (pathLength == 1 || (frameOverlap == 1 && tailL && pathLength == tailL - 1))
-		{
-			ps.overlapEv = ps.evShade[pathLength];
-			besideNext = !serialize && fusedCam && !(frameOverlap == 1 && tailL && pathLength + 1 < tailL);   /* the final overlapEv */
-			/* after this launch only the path tail (in place) or the last bounce (no extension rays) runs: both use the
-			   buffer this launch writes, 1 - ps.in */
-			ps.busy = 1 - ps.in;
-			ps.earlyOk = tailL && pathLength == tailL - 1;   /* config 2 (no tail): no gain, and the fold costs (r04b) */
-		}
+	/* the core stream waits for a primary launch beside the previous frame, unless the first shade launch follows it there */
+	if (primStream != stream && !p.early) CHK_HIP( hipStreamWaitEvent( stream, ps.evTrace[1], 0 ) );
+	ps.Stamp( ps.fromTrace[1], ps.evTrace[1] );
+}
 
-		if (pathLength == maxPL) break;
-		if (primeRef && shadows)
+/* bounces 2 .. of the path: a closest-hit launch; beside the next frame's primary launch (FramePlan::besideNext) a smaller one */
+void RenderCore::TraceBounce( Frame& f, int pathLength )
+{
+	const FramePlan& p = f.plan;
+	const bool beside = p.besideNext && pathLength > p.overlapL;
+	TraceArgs ta = BounceArgs( f, pathLength, ps.Bounce( f.in ) );
+	ta.traceWaves = beside ? 7u : (uint32_t)p.traceWaves;
+	LaunchClosest( f, ta, beside ? p.besideGrid : p.closestGrid, pathLength, stream );
+	ps.Stamp( ps.fromTrace[pathLength], ps.evTrace[pathLength] );
+}
+
+/* the shade launch of a bounce: its last block hands off to the next bounce (no launch of its own; FramePlan::handOffLaunch:
+   a launch does).  The first bounce of a frame with a primary stage of its own reads the primary buffers */
+void RenderCore::ShadeBounce( Frame& f, int pathLength )
+{
+	const FramePlan& p = f.plan;
+	Counters* const c = f.s.c;
+	ShadeParams sp = ShadeArgs( f, pathLength );
+	sp.segCounts = c->segPath[(pathLength - 1) & 1], sp.segOut = c->segPath[pathLength & 1], sp.segStride = p.segStride;
+	sp.segBack = c->segBack[(pathLength - 1) & 1], sp.segOutBack = c->segBack[pathLength & 1];
+	/* two-ended path segments: rays with a chord through the scene box below chordSplit x its largest
+	   extent go last (setting "chordSplit"; 0: off) */
+	const float ext = std::max( std::max( sceneHi[0] - sceneLo[0], sceneHi[1] - sceneLo[1] ), sceneHi[2] - sceneLo[2] );
+	for (int k = 0; k < 3; k++) sp.chordLo[k] = sceneLo[k], sp.chordHi[k] = sceneHi[k];
+	sp.chordCut = ext > 0 ? chordSplit * ext : 0.0f;
+	sp.advance = pathLength < p.maxPL && !p.handOffLaunch;
+	sp.adv = HandOff( f, pathLength );
+	f.snapped = f.snapped || sp.adv.shadowSnap;
+	(pathLength == 1 && p.pFrame ? ps.Primary( ps.fp ) : ps.Bounce( f.in )).In( sp );
+	ps.Bounce( 1 - f.in ).Out( sp );
+	sp.primeRef = primeRef;
+	sp.terminal = p.terminal && pathLength > 1;
+	sp.R0 = (uint32_t)samplesTaken * 7907u + (uint32_t)pathLength * 91771u;
+	if (pathLength == 1 && p.fusedCam && f.hvReadBlock)
+	{
+		/* the block this frame's packets read is the one the next frame records into */
+		sp.hvZero = f.hvReadBlock, sp.hvZeroWords = LH2_HV_MASK + ps.hvMaskWords;
+		ps.hvNextZeroed = true;
+	}
+	const bool earlyHere = p.early && pathLength == 1;
+	if (earlyHere) sp.acc = f.s.delta;   /* the previous frame's finalize may not have read the accumulator yet */
+	lh2_launch_shade( &f.sd, &sp, p.shadeGrid, { nullptr, ps.evShade[pathLength] }, earlyHere ? aheadStream : stream );
+	if (earlyHere) CHK_HIP( hipStreamWaitEvent( stream, ps.evShade[pathLength], 0 ) );
+	ps.Stamp( ps.fromShade[pathLength], ps.evShade[pathLength] );
+	if (pathLength == 1 || pathLength == p.overlapL)
+	{
+		/* the next frame's primary launch starts after this launch (FramePlan::overlapL: the final one).  After it only the
+		   path tail (in place) or the last bounce (no extension rays) runs: both use the buffer this launch writes, 1 - f.in */
+		ps.overlapEv = ps.evShade[pathLength];
+		ps.busy = 1 - f.in;
+		ps.earlyOk = p.tailL && pathLength == p.tailL - 1;   /* config 2 (no tail): no gain, and the fold costs (r04b) */
+	}
+}
+
+/* the path tail: trace and shade every remaining bounce in one launch; each path's records are updated in place, its
+   shadow rays queued for the shadow launch, and rayLog counted.  No shade interval of its own (Synchronize) */
+void RenderCore::PathTail( Frame& f, int pathLength )
+{
+	const FramePlan& p = f.plan;
+	const PathSet io = ps.Bounce( f.in );
+	TraceArgs ta = BounceArgs( f, pathLength, io );
+	ta.shadeBatch = (uint32_t)pathTailBatch, ta.tailWaves = p.tailWaves;
+	ShadeParams sp = ShadeArgs( f, pathLength );
+	io.In( sp ), io.Out( sp );
+	sp.hits = nullptr;   /* the tail shades the hits it finds itself */
+	sp.adv.rayCountLog = f.s.rayLog;
+	lh2_launch_trace_path( &f.sd, &ta, &sp, p.tailGrid, { nullptr, ps.evTrace[pathLength] }, stream );
+	if (p.overlap)
+	{
+		/* the shadow rays of the bounces before the tail, beside it on the side stream (segment counts:
+		   the snapshot; the final launch's work-queue heads start behind them) */
+		CHK_HIP( hipStreamWaitEvent( sideStream, ps.prevStop, 0 ) );
+		const TraceArgs ts = ShadowArgs( f.s, f.s.shSnap, LH2_SHADOW_SLOT + 1, kShadowLeafBatch, ps.sideStack.ptr );
+		lh2_launch_trace_any( &f.sd, &ts, p.sideGrid, 1, { nullptr, ps.evSide }, sideStream );
+		ps.fromSide = ps.prevStop;
+		f.sideOn = true;
+	}
+	ps.Stamp( ps.fromTrace[pathLength], ps.evTrace[pathLength] );
+	f.tailL = pathLength;
+}
+
+/* the bounce loop: the primary rays are traced already (PrimaryStage); bounce 1 only shades them */
+void RenderCore::BounceLoop( Frame& f )
+{
+	const FramePlan& p = f.plan;
+	for (int pathLength = 1; pathLength <= p.maxPL; pathLength++)
+	{
+		f.pl = pathLength;
+		if (pathLength == p.tailL) { PathTail( f, pathLength ); break; }
+		if (pathLength > 1) TraceBounce( f, pathLength );
+		ShadeBounce( f, pathLength );
+		if (pathLength == p.maxPL) break;
+		if (p.bounceShadows)
 		{
-			/* RenderCore_PrimeRef traces the shadow rays of every bounce right after it (rendercore.cpp
-			   connect step), fused with finalizeConnections */
-			TraceArgs ts{};
-			ts.version = TraceVersion();
-			ts.rayO = shO, ts.rayD = shD, ts.segCounts = c->segShadow, ts.segStride = ps.shadowStride;
-			ts.cursor = cursors + (size_t)(LH2_MAX_BOUNCES + pathLength) * LH2_CURSOR_WORDS;
-			ts.refill = (uint32_t)refillOther, ts.leafBatch = (uint32_t)leafBatch;
-			ts.mask = shMask, ts.potentials = shP, ts.acc = accumulator.ptr, ts.gstack = ps.gstack.ptr;
-			lh2_launch_trace_any( &sd, &ts, grid, 1, { nullptr, ps.evShadowB[pathLength] }, stream );
-			ps.fromShadowB[pathLength] = ps.prevStop, ps.prevStop = ps.evShadowB[pathLength];
+			const TraceArgs ts = ShadowArgs( f.s, f.s.c->segShadow, LH2_MAX_BOUNCES + pathLength, leafBatch, ps.gstack.ptr );
+			lh2_launch_trace_any( &f.sd, &ts, p.traceGrid, 1, { nullptr, ps.evShadowB[pathLength] }, stream );
+			ps.Stamp( ps.fromShadowB[pathLength], ps.evShadowB[pathLength] );
 		}
 		/* the hand-off writes this bounce's extension-ray count into the pinned activeLog itself */
 		ps.countReady[pathLength] = ps.evShade[pathLength];
-		if (primeRef)
+		if (p.handOffLaunch)
 		{
-			lh2_launch_counters_next( c, &adv, pathLength, 1, { nullptr, ps.evCount[pathLength] }, stream );
+			const BounceAdvance adv = HandOff( f, pathLength );
+			lh2_launch_counters_next( f.s.c, &adv, pathLength, 1, { nullptr, ps.evCount[pathLength] }, stream );
 			ps.prevStop = ps.countReady[pathLength] = ps.evCount[pathLength];
 		}
 		/* early exit without stalling the GPU: wait for the count of the previous bounce while this one is
@@ -1379,76 +1452,79 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 			CHK_HIP( hipEventSynchronize( ps.countReady[pathLength - 1] ) );
 			if (ps.activeLog[pathLength - 1] == 0) break;
 		}
-		ps.in = 1 - ps.in;
+		f.in = 1 - f.in;
 	}
 	/* an early frame whose paths all ended before the shade launch before its path tail (pathTail >= 4, e.g. every primary
 	   ray misses): its overlap event is still its first shade launch, on the ahead stream, which never waited for the
 	   previous frame's finalize; the next frame's counter resets on this parity's block two frames on order themselves after
 	   overlapEv only.  So it moves to the core stream, behind the previous frame's finalize */
-	if (early && ps.overlapEv == ps.evShade[1])
+	if (p.early && ps.overlapEv == ps.evShade[1])
 	{
 		CHK_HIP( hipEventRecord( ps.evEarlyEnd, stream ) );
 		ps.overlapEv = ps.evEarlyEnd;
 	}
+}
+
+/* the frame's shadow rays (those the side launch did not take) + fused finalizeConnections (rendercore.cpp:575-592) */
+void RenderCore::FinalShadows( Frame& f )
+{
 	/* a snapshot whose side launch did not happen (the frame ended before its path tail): the final launch
 	   traces every shadow ray, from the first */
-	if (snapped && !ps.sideOn)
-		CHK_HIP( hipMemsetAsync( cursors + (size_t)LH2_SHADOW_SLOT * LH2_CURSOR_WORDS, 0, sizeof( uint32_t ) * LH2_CURSOR_WORDS, stream ) );
-	/* shadow rays + fused finalizeConnections (rendercore.cpp:575-592) */
-	if (!primeRef && shadows)
-	{
-		TraceArgs ta{};
-		ta.version = TraceVersion();
-		ta.rayO = shO, ta.rayD = shD, ta.segCounts = c->segShadow, ta.segStride = ps.shadowStride;
-		ta.cursor = cursors + (size_t)LH2_SHADOW_SLOT * LH2_CURSOR_WORDS;
-		ta.refill = (uint32_t)refillOther, ta.leafBatch = (uint32_t)kShadowLeafBatch;
-		ta.mask = shMask, ta.potentials = shP, ta.acc = accumulator.ptr, ta.gstack = ps.gstack.ptr;
-		/* the global stack (gstack) is sized for maxBlocksPerCU blocks per CU: the grid stays within it */
-		lh2_launch_trace_any( &sd, &ta, finalShadowBlocks > 0 ? smCount * std::min( finalShadowBlocks, maxBlocksPerCU ) : grid, 1, { nullptr, ps.evShadow }, stream );
-		ps.fromShadow = ps.prevStop;
-	}
+	if (f.snapped && !f.sideOn)
+		CHK_HIP( hipMemsetAsync( f.s.Cursor( LH2_SHADOW_SLOT ), 0, sizeof( uint32_t ) * LH2_CURSOR_WORDS, stream ) );
+	if (!f.plan.finalShadows) return;
+	const TraceArgs ta = ShadowArgs( f.s, f.s.c->segShadow, LH2_SHADOW_SLOT, kShadowLeafBatch, ps.gstack.ptr );
+	lh2_launch_trace_any( &f.sd, &ta, f.plan.finalShadowGrid, 1, { nullptr, ps.evShadow }, stream );
+	ps.fromShadow = ps.prevStop;
+}
+
+/* the side-stream join, the filter chain or the finalize launch, the display copy and the record of the frame */
+void RenderCore::FinishFrame( Frame& f )
+{
+	const FramePlan& p = f.plan;
 	/* the side launch's contributions are in the accumulator before the frame is finalized */
-	if (ps.sideOn) CHK_HIP( hipStreamWaitEvent( stream, ps.evSide, 0 ) );
+	if (f.sideOn) CHK_HIP( hipStreamWaitEvent( stream, ps.evSide, 0 ) );
 	samplesTaken += scrspp;
 	/* finalize also delivers the frame's counters and ray-count log, and the scene error, to hostStats */
-	const FrameStatsDev fs{ c, rayLog + 1, &hostStats->counters, hostStats->rayCount + 1, SceneErr( frameTlas ), &hostStats->sceneError,
-		cursors + (size_t)primSlot * LH2_CURSOR_WORDS, early ? frameDelta : nullptr };
+	const FrameStatsDev fs{ f.s.c, f.s.rayLog + 1, &hostStats->counters, hostStats->rayCount + 1, SceneErr( f.tlas ), &hostStats->sceneError,
+		f.s.Cursor( kPrimarySlot ), p.early ? f.s.delta : nullptr };
 	/* a tile finalizes its own rows only (a rank of the band partition: the gathered frame is finalized
 	   where it is assembled, MultiDevice / FinalizeFrame) */
 	RowMap rm{};
-	if (tileRows < scrheight) rm = { scrwidth, cp.y0, cp.band, cp.bandStride, tileRows };
+	if (p.tileRows < scrheight) rm = { scrwidth, f.cp.y0, f.cp.band, f.cp.bandStride, p.tileRows };
 	/* the previous frame's end stays recorded (evFrame[2]): an overlapped frame's render time starts at the later of
 	   its primary launch's start and the previous frame's end (Synchronize), so per-frame times sum to wall time */
 	std::swap( evFrame[1], evFrame[2] );
-	prevFrameEndValid = frameEndRecorded, frameWasOverlapped = pFrame && !serialize;
-	frameFiltered = filt;
-	if (filt)
+	prevFrameEndValid = frameEndRecorded;
+	if (p.filt)
 	{
 		/* the filter chain writes the frame; the finalize launch only delivers the statistics (no pixels).  The next frame stays
 		   behind this one */
-		RunFilter( view );
+		RunFilter( f.view );
 		lh2_launch_finalize( accumulator.ptr, frame.ptr, 0, 1.0f, &fs, { nullptr, evFrame[1] }, stream, nullptr );
 		ps.relaid = true;
 	}
 	else lh2_launch_finalize( accumulator.ptr, frame.ptr, scrwidth * scrheight, 1.0f / (float)samplesTaken, &fs, { nullptr, evFrame[1] }, stream, &rm );
 	frameEndRecorded = true;
-	CHK_HIP( hipEventRecord( evTlasFree[frameTlas], stream ) );   /* the next update of this TLAS slot waits for it */
-	tlasFreeValid[frameTlas] = true;
-	if (glResource && !displayAtFinalize)
-	{
-		hipArray_t arr = nullptr;
-		CHK_HIP( hipGraphicsMapResources( 1, &glResource, stream ) );
-		CHK_HIP( hipGraphicsSubResourceGetMappedArray( &arr, glResource, 0, 0 ) );
-		CHK_HIP( hipMemcpy2DToArrayAsync( arr, 0, 0, frame.ptr, sizeof( float4 ) * scrwidth, sizeof( float4 ) * scrwidth, scrheight, hipMemcpyDeviceToDevice, stream ) );
-		CHK_HIP( hipGraphicsUnmapResources( 1, &glResource, stream ) );
-	}
+	CHK_HIP( hipEventRecord( evTlasFree[f.tlas], stream ) );   /* the next update of this TLAS slot waits for it */
+	tlasFreeValid[f.tlas] = true;
+	if (glResource && !displayAtFinalize) CopyFrameToDisplay();
 	hostStats->rayCount[0] = ps.count;
-	ps.lastFused = pFrame, ps.lastSceneVersion = sceneVersion;
-	framePathLengths = ps.tailL ? maxPL : ps.pl;
-	framePrimeRef = primeRef;
+	ps.lastFused = p.pFrame, ps.lastSceneVersion = sceneVersion;
+	last = { f.pl, f.tailL, f.tailL ? p.maxPL : f.pl, p.early, f.sideOn, p.shadows, primeRef != 0, p.filt, p.pFrame && !p.serialize };
 	statsPending = true;
-	frameHostMs = std::chrono::duration<double, std::milli>( std::chrono::high_resolution_clock::now() - t0 ).count();
 }
+
+/* the finalized frame into the registered GL texture (SetInteropTexture) */
+void RenderCore::CopyFrameToDisplay()
+{
+	hipArray_t arr = nullptr;
+	CHK_HIP( hipGraphicsMapResources( 1, &glResource, stream ) );
+	CHK_HIP( hipGraphicsSubResourceGetMappedArray( &arr, glResource, 0, 0 ) );
+	CHK_HIP( hipMemcpy2DToArrayAsync( arr, 0, 0, frame.ptr, sizeof( float4 ) * scrwidth, sizeof( float4 ) * scrwidth, scrheight, hipMemcpyDeviceToDevice, stream ) );
+	CHK_HIP( hipGraphicsUnmapResources( 1, &glResource, stream ) );
+}
+
 
 /* the denoise chain of a frame (reference rendercore.cpp:827-862): prepare, three a-trous passes (the last one writes the
    frame), then the buffers change roles for the next frame */
@@ -1515,7 +1591,7 @@ void RenderCore::GetFilterBuffer( int which, void* out )
 void RenderCore::GetFilterTimes( float* ms4 )
 {
 	Synchronize();
-	for (int k = 0; k < 4; k++) ms4[k] = frameFiltered ? fl.ms[k] : 0.0f;
+	for (int k = 0; k < 4; k++) ms4[k] = last.filtered ? fl.ms[k] : 0.0f;
 }
 
 /* one kernel of the chain on host arrays (lh2_FilterUnit): uploads what the stage reads, runs it, copies back what it writes */
@@ -1574,14 +1650,7 @@ void RenderCore::FinalizeFrame()
 {
 	if (!samplesTaken) return;
 	lh2_launch_finalize( accumulator.ptr, frame.ptr, scrwidth * scrheight, 1.0f / (float)samplesTaken, nullptr, {}, stream );
-	if (glResource)
-	{
-		hipArray_t arr = nullptr;
-		CHK_HIP( hipGraphicsMapResources( 1, &glResource, stream ) );
-		CHK_HIP( hipGraphicsSubResourceGetMappedArray( &arr, glResource, 0, 0 ) );
-		CHK_HIP( hipMemcpy2DToArrayAsync( arr, 0, 0, frame.ptr, sizeof( float4 ) * scrwidth, sizeof( float4 ) * scrwidth, scrheight, hipMemcpyDeviceToDevice, stream ) );
-		CHK_HIP( hipGraphicsUnmapResources( 1, &glResource, stream ) );
-	}
+	if (glResource) CopyFrameToDisplay();
 }
 
 void RenderCore::CopyFrameAsync( void* devDst )
@@ -1624,11 +1693,11 @@ void RenderCore::Synchronize()
 	auto ms = [&]( hipEvent_t a, hipEvent_t b ) { float t = 0; (void)hipEventElapsedTime( &t, a, b ); return t * 1e-3f; };
 	/* each interval: the previous launch's stop event -> this launch's stop event (kernel + launch gap) */
 	auto trace = [&]( int L ) {
-		if (L > ps.pl) return 0.0f;
+		if (L > last.pl) return 0.0f;
 		float t = ms( ps.fromTrace[L], ps.evTrace[L] );
 		/* early shade: the second bounce's interval starts at the first shade launch's stop (ahead stream); the part
 		   before the previous frame's end is the previous frame's */
-		if (L == 2 && ps.early && prevFrameEndValid)
+		if (L == 2 && last.early && prevFrameEndValid)
 		{
 			const float shared = ms( ps.fromTrace[L], evFrame[2] );
 			if (shared > 0) t = std::max( 0.0f, t - shared );
@@ -1637,37 +1706,37 @@ void RenderCore::Synchronize()
 	};
 	coreStats.primaryRayCount = rc[0];
 	coreStats.traceTime0 = trace( 1 );
-	coreStats.bounce1RayCount = framePathLengths >= 2 ? rc[1] : 0;
-	coreStats.traceTime1 = framePathLengths >= 2 ? trace( 2 ) : 0;
+	coreStats.bounce1RayCount = last.pathLengths >= 2 ? rc[1] : 0;
+	coreStats.traceTime1 = last.pathLengths >= 2 ? trace( 2 ) : 0;
 	coreStats.deepRayCount = 0, coreStats.traceTimeX = 0;
 	/* (a path tail's bounces past its first have no launch of their own: their time is in its launch) */
-	for (int L = 3; L <= framePathLengths; L++)
+	for (int L = 3; L <= last.pathLengths; L++)
 	{
 		coreStats.deepRayCount = rc[L - 1];
-		if (L <= ps.pl) coreStats.traceTimeX = trace( L );
+		if (L <= last.pl) coreStats.traceTimeX = trace( L );
 	}
 	float shadow = 0, shade = 0;
-	if (frameShadows && !framePrimeRef)
-		shadow = ms( ps.fromShadow, ps.evShadow ) + (ps.sideOn ? ms( ps.fromSide, ps.evSide ) : 0.0f);
-	else if (frameShadows) for (int L = 1; L < ps.pl; L++) shadow += ms( ps.fromShadowB[L], ps.evShadowB[L] );
-	for (int L = 1; L <= ps.pl; L++) if (L != ps.tailL) shade += ms( ps.fromShade[L], ps.evShade[L] );
+	if (last.shadows && !last.primeRef)
+		shadow = ms( ps.fromShadow, ps.evShadow ) + (last.sideOn ? ms( ps.fromSide, ps.evSide ) : 0.0f);
+	else if (last.shadows) for (int L = 1; L < last.pl; L++) shadow += ms( ps.fromShadowB[L], ps.evShadowB[L] );
+	for (int L = 1; L <= last.pl; L++) if (L != last.tailL) shade += ms( ps.fromShade[L], ps.evShade[L] );
 	coreStats.shadowTraceTime = shadow;
 	coreStats.shadeTime = shade;
 	coreStats.filterTime = 0;
-	if (frameFiltered)
+	if (last.filtered)
 	{
 		coreStats.filterTime = ms( fl.ev[0], fl.ev[4] );
 		for (int k = 0; k < 4; k++) fl.ms[k] = ms( fl.ev[k], fl.ev[k + 1] ) * 1e3f;
 	}
-	for (int L = 1; L <= framePathLengths && L <= 8; L++) lastKernelMs[L - 1] = trace( L ) * 1e3f;
-	coreStats.totalShadowRays = framePrimeRef ? cn.totalShadowRays : QueuedShadowRays( cn );
+	for (int L = 1; L <= last.pathLengths && L <= 8; L++) lastKernelMs[L - 1] = trace( L ) * 1e3f;
+	coreStats.totalShadowRays = last.primeRef ? cn.totalShadowRays : QueuedShadowRays( cn );
 	coreStats.totalExtensionRays = cn.totalExtensionRays;
 	coreStats.totalRays = coreStats.totalExtensionRays + coreStats.totalShadowRays;
 	/* device time of the whole frame (the reference's Render blocks).  Under frameOverlap the frame's primary launch
 	   starts beside the previous frame's tail: the part before the previous frame's end is the previous frame's
 	   (ADVICE r3).  traceTime0 stays the primary launch's own duration, stretched by what ran beside it */
 	coreStats.renderTime = ms( evFrame[0], evFrame[1] );
-	if (frameWasOverlapped && prevFrameEndValid)
+	if (last.overlapped && prevFrameEndValid)
 	{
 		const float shared = ms( evFrame[0], evFrame[2] );
 		if (shared > 0) coreStats.renderTime = std::max( 0.0f, coreStats.renderTime - shared );
@@ -1684,23 +1753,24 @@ lh2_CoreStats RenderCore::GetCoreStats()
 void RenderCore::GetRayCounts( uint32_t* out17 )
 {
 	Synchronize();
-	for (int i = 0; i < 16; i++) out17[i] = i < framePathLengths ? hostStats->rayCount[i] : 0u;
-	out17[16] = framePrimeRef ? hostStats->counters.totalShadowRays : QueuedShadowRays( hostStats->counters );
+	for (int i = 0; i < 16; i++) out17[i] = i < last.pathLengths ? hostStats->rayCount[i] : 0u;
+	out17[16] = last.primeRef ? hostStats->counters.totalShadowRays : QueuedShadowRays( hostStats->counters );
 }
 
 int RenderCore::DebugShadowRays( float* o4, float* d4, float* p4, int cap )
 {
 	Synchronize();
 	int n = 0;
+	const FrameSlots s = Slots();   /* the last frame's parity */
 	for (int k = 0; k < LH2_SEGS; k++)
 	{
 		const uint32_t cnt = std::min( hostStats->counters.segShadow[k * LH2_SEGCOUNT_STRIDE], ps.shadowStride );
 		const int m = std::min( (int)cnt, cap - n );
 		if (m <= 0) break;
-		const size_t at = (size_t)ps.fp * ps.shCap + (size_t)k * ps.shadowStride;   /* the last frame's parity */
-		CHK_HIP( hipMemcpy( o4 + 4 * (size_t)n, ps.shO.ptr + at, 16 * (size_t)m, hipMemcpyDeviceToHost ) );
-		CHK_HIP( hipMemcpy( d4 + 4 * (size_t)n, ps.shD.ptr + at, 16 * (size_t)m, hipMemcpyDeviceToHost ) );
-		CHK_HIP( hipMemcpy( p4 + 4 * (size_t)n, ps.shP.ptr + at, 16 * (size_t)m, hipMemcpyDeviceToHost ) );
+		const size_t at = (size_t)k * ps.shadowStride;
+		CHK_HIP( hipMemcpy( o4 + 4 * (size_t)n, s.shO + at, 16 * (size_t)m, hipMemcpyDeviceToHost ) );
+		CHK_HIP( hipMemcpy( d4 + 4 * (size_t)n, s.shD + at, 16 * (size_t)m, hipMemcpyDeviceToHost ) );
+		CHK_HIP( hipMemcpy( p4 + 4 * (size_t)n, s.shP + at, 16 * (size_t)m, hipMemcpyDeviceToHost ) );
 		n += m;
 	}
 	return n;
@@ -1788,6 +1858,19 @@ void RenderCore::GetFrame( float* hostOut4 )
 	CHK_HIP( hipMemcpy( hostOut4, frame.ptr, sizeof( float4 ) * (size_t)scrwidth * scrheight, hipMemcpyDeviceToHost ) );
 }
 
+/* a unit query over n dense rays; hits non-null: a closest-hit query, traced as the settings "unitCoherent" (as the frame
+   traces its tiled primary rays) and "unitTraceWaves" say */
+TraceArgs RenderCore::UnitArgs( const float4* o, const float4* d, int n, uint32_t* cursor, int* gstack, uint4* hits ) const
+{
+	TraceArgs ta{};
+	ta.version = TraceVersion();
+	ta.rayO = o, ta.rayD = d, ta.countFixed = (uint32_t)n, ta.segStride = (uint32_t)((n + LH2_SEGS - 1) / LH2_SEGS), ta.cursor = cursor;
+	ta.hits = hits, ta.gstack = gstack;
+	ta.refill = (uint32_t)refillOther, ta.leafBatch = (uint32_t)leafBatch;
+	if (hits) ta.packet = unitCoherent && UsePackets() ? 1 : 0, ta.traceWaves = (uint32_t)unitTraceWaves;
+	return ta;
+}
+
 void RenderCore::TraceClosest( const float* ot, const float* dt, int n, uint32_t* hits4 )
 {
 	if (geometryDirty || instancesDirty) UpdateToplevel();
@@ -1797,12 +1880,7 @@ void RenderCore::TraceClosest( const float* ot, const float* dt, int n, uint32_t
 	gs.resize( (size_t)(LH2_STACK_TOTAL - LH2_STACK_LDS) * TraceGrid() * 256 );
 	CHK_HIP( hipMemsetAsync( ovf.ptr, 0, sizeof( uint32_t ) * LH2_CURSOR_WORDS, stream ) );
 	const SceneDev sd = MakeSceneDev();
-	TraceArgs ta{};
-	ta.version = TraceVersion();
-	ta.rayO = o.ptr, ta.rayD = d.ptr, ta.countFixed = (uint32_t)n, ta.segStride = (uint32_t)((n + LH2_SEGS - 1) / LH2_SEGS), ta.cursor = ovf.ptr, ta.hits = h.ptr, ta.gstack = gs.ptr;
-	ta.refill = (uint32_t)refillOther, ta.leafBatch = (uint32_t)leafBatch;
-	ta.packet = unitCoherent && UsePackets() ? 1 : 0;
-	ta.traceWaves = (uint32_t)unitTraceWaves;
+	const TraceArgs ta = UnitArgs( o.ptr, d.ptr, n, ovf.ptr, gs.ptr, h.ptr );
 	lh2_launch_trace_closest( &sd, &ta, ta.packet ? PacketGrid() : UnitGrid(), {}, stream );
 	CHK_HIP( hipMemcpyAsync( hits4, h.ptr, sizeof( uint4 ) * (size_t)n, hipMemcpyDeviceToHost, stream ) );
 	CHK_HIP( hipStreamSynchronize( stream ) );
@@ -1820,9 +1898,8 @@ void RenderCore::TraceAny( const float* ot, const float* dt, int n, uint32_t* oc
 	CHK_HIP( hipMemsetAsync( ovf.ptr, 0, sizeof( uint32_t ) * LH2_CURSOR_WORDS, stream ) );
 	CHK_HIP( hipMemsetAsync( m.ptr, 0, words * 4, stream ) );
 	const SceneDev sd = MakeSceneDev();
-	TraceArgs ta{};
-	ta.version = TraceVersion();
-	ta.rayO = o.ptr, ta.rayD = d.ptr, ta.countFixed = (uint32_t)n, ta.segStride = (uint32_t)((n + LH2_SEGS - 1) / LH2_SEGS), ta.cursor = ovf.ptr, ta.mask = m.ptr, ta.gstack = gs.ptr, ta.refill = (uint32_t)refillOther, ta.leafBatch = (uint32_t)leafBatch;
+	TraceArgs ta = UnitArgs( o.ptr, d.ptr, n, ovf.ptr, gs.ptr, nullptr );
+	ta.mask = m.ptr;
 	lh2_launch_trace_any( &sd, &ta, TraceGrid(), 0, {}, stream );
 	std::vector<uint32_t> tmp( words );
 	CHK_HIP( hipMemcpyAsync( tmp.data(), m.ptr, words * 4, hipMemcpyDeviceToHost, stream ) );
@@ -1854,20 +1931,13 @@ void RenderCore::TraceClosestDevice( const void* ro, const void* rd, int n, void
 	for (auto& e : ev) CHK_HIP( hipEventCreate( &e ) );
 	for (int i = 0; i < iterations; i++)
 	{
-		TraceArgs ta{};
-		ta.version = TraceVersion();
-		ta.rayO = (const float4*)ro, ta.rayD = (const float4*)rd, ta.countFixed = (uint32_t)n, ta.segStride = (uint32_t)((n + LH2_SEGS - 1) / LH2_SEGS), ta.cursor = cursors.ptr + (size_t)i * LH2_CURSOR_WORDS;
-		ta.hits = (uint4*)hitsOut, ta.gstack = ps.gstack.ptr;
-			/* unitCoherent: trace as the frame traces its (tiled) primary rays */
-		ta.refill = (uint32_t)refillOther, ta.leafBatch = (uint32_t)leafBatch;
-		ta.packet = unitCoherent && UsePackets() ? 1 : 0;
+		TraceArgs ta = UnitArgs( (const float4*)ro, (const float4*)rd, n, cursors.ptr + (size_t)i * LH2_CURSOR_WORDS, ps.gstack.ptr, (uint4*)hitsOut );
 #ifdef LH2_TRACE_STATS
 		ta.stats = tstats.ptr;
 #endif
 #ifdef LH2_TRACE_TIMES
 		ta.stats = ttimes.ptr;
 #endif
-		ta.traceWaves = (uint32_t)unitTraceWaves;
 		lh2_launch_trace_closest( &sd, &ta, ta.packet ? PacketGrid() : UnitGrid(), { ev[2 * i], ev[2 * i + 1] }, stream );
 	}
 	CHK_HIP( hipStreamSynchronize( stream ) );
@@ -1902,9 +1972,7 @@ void RenderCore::GenerateEyeRays( const lh2_ViewPyramid& view, uint32_t R0, int 
 	DevBuf<float4> o, d, t4, q4;
 	o.resize( n ), d.resize( n ), t4.resize( n ), q4.resize( n );
 	CameraParams cp{};
-	cp.pos = view.pos, cp.p1 = view.p1;
-	cp.right = { view.p2.x - view.p1.x, view.p2.y - view.p1.y, view.p2.z - view.p1.z };
-	cp.up = { view.p3.x - view.p1.x, view.p3.y - view.p1.y, view.p3.z - view.p1.z };
+	SetCameraView( cp, view );
 	cp.aperture = view.aperture, cp.distortion = view.distortion, cp.geometryEpsilon = geometryEpsilon;
 	cp.w = scrwidth, cp.h = scrheight, cp.pass = pass, cp.R0 = R0;
 	cp.y0 = 0, cp.tileRows = scrheight, cp.band = scrheight, cp.bandStride = scrheight, cp.tiled = 0, cp.primeRef = primeRef;

@@ -74,8 +74,30 @@ struct CoreMeshHost   /* RenderCore always copies what it needs (rendercore.h:57
 
 struct CoreInstanceHost { int mesh; float T[16]; float inv[16]; };
 
+/* one set of path buffers: rays, path state and hits.  A launch reads one set and (a shade launch) writes another */
+struct PathSet
+{
+	float4 *O, *D, *T4, *Q4;
+	uint4* hits;
+	void Rays( TraceArgs& a ) const { a.rayO = O, a.rayD = D, a.hits = hits; }
+	void In( ShadeParams& p ) const { p.rayO = O, p.rayD = D, p.T4 = T4, p.Q4 = Q4, p.hits = hits; }
+	void Out( ShadeParams& p ) const { p.rayOut = O, p.rayDOut = D, p.T4Out = T4, p.Q4Out = Q4; }
+};
+
+/* what the launches of one frame parity own (PathStreams: "per frame parity") */
+struct FrameSlots
+{
+	Counters* c;
+	uint32_t *cursors, *rayLog;
+	float4 *shO, *shD, *shP;
+	uint32_t *shMask, *shSnap;           /* shSnap: the shadow rays queued before the path tail */
+	float4* delta;
+	uint32_t* Cursor( int slot ) const { return cursors + (size_t)slot * LH2_CURSOR_WORDS; }   /* a launch's work-queue heads (LH2_CURSOR_SLOTS) */
+};
+
 /* the frame's path and ray streams (segmented, lh2_kernels.h) with their counters, work-queue heads,
-   traversal stacks and the events that time the frame's launches */
+   traversal stacks and the events that time the frame's launches.  Buffers, events and the state that crosses frames
+   (marked "crosses frames"); what Synchronize needs to know about the last frame is RenderCore::last */
 struct PathStreams
 {
 	size_t cap = 0;                      /* paths the buffers hold */
@@ -86,6 +108,8 @@ struct PathStreams
 	   frame's later bounces */
 	DevBuf<float4> rayOP[2], rayDP[2], T4P[2], Q4P[2];   /* per frame parity */
 	DevBuf<uint4> hitsP[2];
+	PathSet Bounce( int i ) const { return { rayO[i].ptr, rayD[i].ptr, T4[i].ptr, Q4[i].ptr, hits.ptr }; }
+	PathSet Primary( int parity ) const { return { rayOP[parity].ptr, rayDP[parity].ptr, T4P[parity].ptr, Q4P[parity].ptr, hitsP[parity].ptr }; }
 	DevBuf<float4> shO, shD, shP;        /* 2 x shCap (frame parity) */
 	DevBuf<uint32_t> shMask;             /* 2 x shMaskWords */
 	size_t shCap = 0, shMaskWords = 0;
@@ -99,38 +123,79 @@ struct PathStreams
 	DevBuf<uint32_t> cursors;            /* 2 x LH2_CURSOR_SLOTS x LH2_CURSOR_WORDS work-queue heads */
 	DevBuf<uint32_t> rayLog;             /* 2 x LH2_RAYLOG */
 	DevBuf<uint32_t> hv;                 /* heavy-first packets: two blocks (TraceArgs::hvRead / hvWrite), the frame parity picks */
-	uint32_t hvCap = 0, hvMaskWords = 0, hvBlock = 0, hvParity = 0;
+	uint32_t hvCap = 0, hvMaskWords = 0, hvBlock = 0;
+	uint32_t hvParity = 0;               /* crosses frames: the block the next frame's packets read */
 	uint32_t* activeLog = nullptr;       /* pinned: extension rays after each bounce (advance_bounce) */
 	/* a launch carries only a stop event (a start event costs its dispatch ~5 us of idle GPU); a timed
 	   interval runs from the previous launch's stop event, so it includes the launch gap */
 	hipEvent_t evTrace[LH2_MAX_BOUNCES + 1] = {}, evShade[LH2_MAX_BOUNCES + 1] = {}, evShadowB[LH2_MAX_BOUNCES + 1] = {};
 	hipEvent_t evCount[LH2_MAX_BOUNCES + 2] = {}, evCamera = nullptr, evShadow = nullptr;
 	hipEvent_t evSide = nullptr, fromSide = nullptr;   /* shadowOverlap: the side launch */
-	bool sideOn = false;                 /* this frame traced its early shadow rays on the side stream */
 	hipEvent_t countReady[LH2_MAX_BOUNCES + 2] = {};   /* [L]: the event after which bounce L's hand-off is done (evShade or evCount, not owned) */
 	hipEvent_t fromTrace[LH2_MAX_BOUNCES + 1] = {}, fromShade[LH2_MAX_BOUNCES + 1] = {}, fromShadowB[LH2_MAX_BOUNCES + 1] = {}, fromShadow = nullptr;
-	/* this frame */
+	hipEvent_t prevStop = nullptr;       /* the stop event of the frame's last timed launch so far */
+	/* a launch with stop event `stop` was queued: its timed interval starts at the previous launch's stop event */
+	void Stamp( hipEvent_t& from, hipEvent_t stop ) { from = prevStop, prevStop = stop; }
+	/* the stream layout of the frame being rendered (after Render: the last frame's) */
 	uint32_t count = 0, segStride = 0, shadowStride = 0;
-	int in = 0, pl = 0;
-	int tailL = 0;                       /* this frame's path-tail launch (pathLength), 0: none */
-	bool hvOn = false;                   /* this frame's primary packets run heavy-first (TraceArgs::hvRead) */
-	/* the camera fused into the primary packet launch (setting "cameraFused"): the heavy-packet block the next frame
-	   records into is zeroed by the frame's first shade launch (hvNextZeroed: it was) */
+	int fp = 0;                          /* its parity */
+	/* crosses frames.  The camera fused into the primary packet launch (setting "cameraFused"): the heavy-packet block the
+	   next frame records into is zeroed by the frame's first shade launch (hvNextZeroed: it was) */
 	bool hvNextZeroed = false;
-	/* frame overlap (setting "frameOverlap"): the primary launch of a fused frame runs on the ahead stream after the
-	   previous frame's first shade launch, unless something since then needs it to wait for the whole previous frame */
+	/* crosses frames.  Frame overlap (setting "frameOverlap"): the primary launch of a fused frame runs on the ahead stream
+	   after the previous frame's first shade launch, unless something since then needs it to wait for the whole previous
+	   frame (relaid: buffers were reallocated or the last frame was filtered) */
 	bool lastFused = false, relaid = true;
 	uint64_t lastSceneVersion = 0;
 	hipEvent_t overlapEv = nullptr;      /* the last frame's shade launch the next primary launch waits for (not owned) */
 	hipEvent_t evEarlyEnd = nullptr;     /* an early frame that ended before its path tail: overlapEv on the core stream (owned) */
-	hipEvent_t prevStop = nullptr;
-	int fp = 0;                          /* this (the last) frame's parity */
-	/* early shade (setting "earlyShade"): the next frame's first shade launch also runs beside this frame's launches
-	   after overlapEv.  Those use one ping-pong buffer (busy: the path tail's, or the last bounce's rays) and write
+	/* crosses frames.  Early shade (setting "earlyShade"): the next frame's first shade launch also runs beside this frame's
+	   launches after overlapEv.  Those use one ping-pong buffer (busy: the path tail's, or the last bounce's rays) and write
 	   neither (earlyOk), so the next frame's first shade writes the other one */
 	int busy = 0;
-	bool earlyOk = false, early = false;
+	bool earlyOk = false;
 };
+
+/* every decision Render makes before it queues anything (RenderCore::PlanFrame): constant for the rest of the frame */
+struct FramePlan
+{
+	bool restart, filt;                  /* the accumulation starts over; the denoise mode runs this frame */
+	int tileRows;
+	uint32_t pathCount, segStride;
+	float aperture;
+	int maxPL, tailL;                    /* bounces at most; the path-tail launch (pathLength), 0: none */
+	bool packets;                        /* the primary rays are traced as packets */
+	bool fusedCam, camAhead;             /* the camera fused into the primary packet launch; camera + per-ray primary launch apart */
+	bool pFrame;                         /* either: the primary stage has buffers of its own and may run beside the previous frame */
+	bool serialize;                      /* ... but runs behind it, on the core stream, this frame */
+	bool early;                          /* the first shade launch follows the primary launch on the ahead stream */
+	bool clearAll, clearByLaunch, clearBehind;   /* how a restart zeroes the accumulator (PlanFrame, BeginFrame) */
+	bool growPaths;                      /* BeginFrame is about to reallocate the path buffers */
+	bool hvOn, hvRelayout;               /* heavy-first primary packets; their blocks are (re)allocated first */
+	uint32_t hvCap, hvTiles;
+	float hvFactor;
+	bool small;                          /* at most kSmallFramePaths paths */
+	bool shadows, overlap;               /* the scene has lights; the shadow rays before the tail go to the side stream */
+	bool bounceShadows, finalShadows, handOffLaunch;   /* PrimeRef's launches after every bounce, or one shadow launch per frame */
+	bool terminal;                       /* ShadeParams::terminal of the bounces past the first */
+	bool besideNext;                     /* the next frame's primary launch will likely run beside this frame's launches after ... */
+	int overlapL;                        /* ... the shade launch of this bounce, the next frame's overlap event */
+	int traceWaves;
+	uint32_t tailWaves;
+	int traceGrid, closestGrid, besideGrid, primaryGrid, shadeGrid, tailGrid, sideGrid, finalShadowGrid;
+};
+
+/* what Synchronize, GetRayCounts and GetCoreStats read about the last rendered frame (written once, at the end of Render) */
+struct LastFrame
+{
+	int pl = 0;                          /* bounces launched */
+	int tailL = 0;                       /* its path-tail launch (pathLength), 0: none */
+	int pathLengths = 0;                 /* path lengths with a ray count (a path tail: all of them) */
+	bool early = false, sideOn = false;  /* its first shade launch ran early; its early shadow rays on the side stream */
+	bool shadows = true, primeRef = false, filtered = false, overlapped = false;
+};
+
+struct Frame;   /* a frame being queued (rendercore.cpp) */
 
 /* the denoise mode's buffers (setting "filter"; lh2_filter.h), allocated only while it is on.  Index cur: the frame being
    rendered (after Render: the last frame's); 1 - cur: the frame before it */
@@ -229,7 +294,7 @@ private:
 	void EnsureBuffers();
 	void EnsureFilterBuffers();
 	void RunFilter( const lh2_ViewPyramid& view );
-	bool filterOn = false, filterAllowed = true, frameFiltered = false;
+	bool filterOn = false, filterAllowed = true;
 	int filterLds = -1;                  /* the a-trous passes' taps from an LDS tile (1), through L1 / L2 (0); -1: the measured pick per pass */
 	float clampDirect = LH2_FILTER_CLAMP_DIRECT, clampIndirect = LH2_FILTER_CLAMP_INDIRECT;
 	FilterState fl;
@@ -247,16 +312,31 @@ private:
 #endif
 	int buildThreads = 0;                /* host threads of the deferred BLAS builds (setting "buildThreads"; 0: LH2_BUILD_THREADS,
 	                                        OMP_NUM_THREADS or min(16, cores)) */
+	bool PathsFit( uint32_t paths ) const { return (size_t)paths + 64 <= ps.cap; }
 	void EnsurePaths( uint32_t paths );
 	void EnsureStack();
+	/* Render's steps: the plan (no HIP call), the state transitions and buffers, then the launch stages */
+	FramePlan PlanFrame( const lh2_ViewPyramid& view, int converge ) const;
+	void BeginFrame( Frame& f, int converge );
+	void PrimaryStage( Frame& f );
+	void BounceLoop( Frame& f );
+	void TraceBounce( Frame& f, int pathLength );
+	void ShadeBounce( Frame& f, int pathLength );
+	void PathTail( Frame& f, int pathLength );
+	void FinalShadows( Frame& f );
+	void FinishFrame( Frame& f );
+	void CopyFrameToDisplay();
+	void LaunchClosest( const Frame& f, const TraceArgs& ta, int grid, int pathLength, hipStream_t st );   /* stop event: evTrace[pathLength] */
+	TraceArgs BounceArgs( const Frame& f, int pathLength, const PathSet& rays ) const;
+	ShadeParams ShadeArgs( const Frame& f, int pathLength ) const;
+	BounceAdvance HandOff( const Frame& f, int pathLength ) const;
+	TraceArgs ShadowArgs( const FrameSlots& s, const uint32_t* segCounts, int cursorSlot, int leafBatch, int* gstack ) const;
+	TraceArgs UnitArgs( const float4* o, const float4* d, int n, uint32_t* cursor, int* gstack, uint4* hits ) const;
 	void CheckSceneError();
 	bool UsePackets() const;
 	SceneDev MakeSceneDev();             /* the latest TLAS slot's scene; the core stream waits for its update (SyncTlas) */
 	void SyncTlas();
-	Counters* FrameCounters() const { return ps.counters.ptr + ps.fp; }
-	uint32_t* FrameCursors() const { return ps.cursors.ptr + (size_t)ps.fp * LH2_CURSOR_SLOTS * LH2_CURSOR_WORDS; }
-	uint32_t* FrameRayLog() const { return ps.rayLog.ptr + (size_t)ps.fp * LH2_RAYLOG; }
-	TraceArgs StreamArgs( const float4* o, const float4* d, const uint32_t* segCounts, uint32_t segStride, uint32_t* cursor, bool coherent ) const;
+	FrameSlots Slots() const;            /* of the frame parity PathStreams::fp */
 	int TraceGrid() const { return smCount * blocksPerCU; }
 	int UnitGrid() const { return smCount * std::min( blocksPerCU, unitTraceWaves == 8 ? traceBlocksPerCU8 : traceBlocksPerCU7 ); }
 	int PacketGrid() const { return smCount * packetBlocksPerCU; }   /* packet kernel: its own occupancy */
@@ -346,13 +426,13 @@ private:
 	DevBuf<float4> delta;                /* early shade: the first shade launch's accumulator additions (FrameStatsDev::delta), per frame parity */
 	PathStreams ps;                      /* on `stream`; also serves the unit-level trace calls */
 	bool tileChanged = false;            /* the next restart clears the whole accumulator, not only the tile's pixels */
-	bool frameShadows = true;            /* the last frame queued shadow-ray launches (the scene has lights) */
+	LastFrame last;
 	bool singleInstanceStart = true;     /* one instance of a non-empty mesh: rays start at its TLAS leaf (SceneDev::tlasRoot) */
 	bool terminalShade = true;           /* k_shade<true> for shade passes whose hits cannot contribute (ShadeParams::terminal) */
 	FrameStats* hostStats = nullptr;     /* pinned */
 	bool statsPending = false;
 	hipEvent_t evFrame[3] = {};          /* the frame's start marker, its end (finalize), the previous frame's end */
-	bool frameEndRecorded = false, prevFrameEndValid = false, frameWasOverlapped = false;
+	bool frameEndRecorded = false, prevFrameEndValid = false;
 	int tiledRays = 1;                   /* primary rays stored in 8x8 pixel blocks per wave (coherent packets) */
 	int cameraFused = 1;                 /* primary rays made by the packet launch itself (k_trace_primary_packet), no camera launch */
 	/* a fused frame's primary launch beside the previous frame's later bounces (aheadStream): 1, after its shade launch
@@ -394,12 +474,9 @@ private:
 	   4K frame -0.9 %, the N = 8 share -0.3 % against 8; 2 and 4 slower, 24 no better; their refill stays refillOther (32 and
 	   60 slower) (profiles/r05f_ab_lazy_frame_shadow_sweep.txt, r05f_ab_shadow_leafbatch.txt) */
 	static constexpr int kShadowLeafBatch = 16;
-#ifndef LH2_PRIMARY_RESETS
-#define LH2_PRIMARY_RESETS 1
-#endif
-	/* an overlapped frame's counter and work-queue resets done by its primary launch (as behind the previous frame), not by
-	   a k_init_counters launch before it on the ahead stream */
-	static constexpr bool kPrimaryResets = LH2_PRIMARY_RESETS != 0;
+	/* the primary launch's work-queue heads: bounce 1's slot of the frame parity's block, left alone by the launch's own resets
+	   and zeroed by the finalize of the frame before the previous one (FrameStatsDev::zeroHeads) */
+	static constexpr int kPrimarySlot = 1;
 #ifndef LH2_CAM_AHEAD
 #define LH2_CAM_AHEAD 1
 #endif
@@ -460,7 +537,6 @@ private:
 	int unitCoherent = 0;
 	int packetPrimary = -1;              /* wave-uniform packet traversal for 8x8-tiled primary rays (-1: by scene size) */
 	int gpuBuild = 0, gpuTlas = 1;       /* BLAS builder (1: GPU PLOC, 0: CPU binned SAH); TLAS on the GPU */
-	int framePathLengths = 0, framePrimeRef = 0;
 	double frameHostMs = 0;
 	int samplesTaken = 0;
 	bool firstConvergingFrame = false;
