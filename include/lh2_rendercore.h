@@ -33,7 +33,8 @@
      lh2_core_copy_accumulator_rows, lh2_core_copy_frame_async, lh2_core_pack_tile, lh2_core_pack_tile_ordered, lh2_core_tile_rows, lh2_core_stream, lh2_core_ray_counts, lh2_core_trace_closest,
      lh2_core_trace_any, lh2_core_trace_closest_device, lh2_core_generate_eye_rays,
      lh2_core_scene_info, lh2_core_debug_shadow_rays, lh2_core_debug_bvh4, lh2_core_debug_poison_tlas, lh2_core_get_setting, lh2_set_device, lh2_xorshift_floats, lh2_version,
-     lh2_core_filter_buffer, lh2_core_filter_times, lh2_core_filter_unit (the denoise mode, setting "filter").
+     lh2_core_filter_buffer, lh2_core_filter_times, lh2_core_filter_unit (the denoise mode, setting "filter"),
+     lh2_core_bsdf_unit (the shade kernels' BSDF on host records).
 */
 #ifndef LH2_RENDERCORE_H
 #define LH2_RENDERCORE_H
@@ -137,6 +138,20 @@ typedef struct
 	const float* in; const float* prev; float* out;
 } lh2_FilterUnit;
 int lh2_core_filter_unit( lh2_core core, const lh2_FilterUnit* unit );
+
+/* the Disney BSDF of the shade kernels (their EvaluateBSDF / SampleBSDF device functions) on n host records, against the
+   materials of lh2_core_set_materials through the kernels' own unpacking of the uploaded records (untextured: the maps
+   are not read).  Per sample 20 floats in: {iN, material index (int bits)}, {N, distance}, {iT, r0}, {wow, r1}, {wiw, -};
+   8 out: {value, pdf}, {wiw, specular (0 / 1, uint bits)}.  sample 0: EvaluateBSDF( iN, iT, wow, wiw ); 1: SampleBSDF( iN,
+   N, iT, wow, distance, r0, r1 ), its wiw and flag starting at 0.  The transmittance is zeroed for dot( -wow, N ) <= 0, as
+   the shade kernels do for a front-side hit.  A material index out of range is an error */
+typedef struct
+{
+	int sample, n;
+	const float* in;    /* n x 20 */
+	float* out;         /* n x 8 */
+} lh2_BsdfUnit;
+int lh2_core_bsdf_unit( lh2_core core, const lh2_BsdfUnit* unit );
 
 /* host utility: n successive RandomFloat() values of Marsaglia xorshift32 (platform/system.cpp:44-46) */
 int lh2_xorshift_floats( uint32_t seed, float* out, uint64_t n );

@@ -85,6 +85,11 @@ class FilterUnit(C.Structure):
                 ("prevMoments", C.c_void_p), ("in_", C.c_void_p), ("prev", C.c_void_p), ("out", C.c_void_p)]
 
 
+class BsdfUnit(C.Structure):
+    """lh2_BsdfUnit (include/lh2_rendercore.h): EvaluateBSDF / SampleBSDF on host records (bsdf_records)."""
+    _fields_ = [("sample", C.c_int), ("n", C.c_int), ("in_", C.c_void_p), ("out", C.c_void_p)]
+
+
 class CoreStats(C.Structure):
     _fields_ = [("deviceName", C.c_char_p), ("SMcount", C.c_uint32), ("ccMajor", C.c_uint32),
                 ("ccMinor", C.c_uint32), ("VRAM", C.c_uint32), ("argb32TexelCount", C.c_uint32),
@@ -188,12 +193,13 @@ def default_material() -> CoreMaterial:
 
 def make_material(color=(1, 1, 1), roughness=None, metallic=None, specular=None, transmission=None, eta=None,
                   absorption=None, sheen=None, clearcoat=None, clearcoatGloss=None, subsurface=None,
-                  smooth: bool = True) -> CoreMaterial:
+                  smooth: bool = True, anisotropic=None, specularTint=None, sheenTint=None) -> CoreMaterial:
     m = default_material()
     m.color.value = float3(*color)
     for name, val in (("roughness", roughness), ("metallic", metallic), ("specular", specular),
                       ("transmission", transmission), ("eta", eta), ("sheen", sheen), ("clearcoat", clearcoat),
-                      ("clearcoatGloss", clearcoatGloss), ("subsurface", subsurface)):
+                      ("clearcoatGloss", clearcoatGloss), ("subsurface", subsurface), ("anisotropic", anisotropic),
+                      ("specularTint", specularTint), ("sheenTint", sheenTint)):
         if val is not None:
             getattr(m, name).value = float(val)
     if absorption is not None:
@@ -207,6 +213,26 @@ def material_array(mats) -> C.Array:
     for i, m in enumerate(mats):
         arr[i] = m
     return arr
+
+
+# --- lh2_BsdfUnit records (include/lh2_rendercore.h): 20 words in, 8 out per sample ---------
+BSDF_IN_WORDS = 20
+BSDF_OUT_WORDS = 8
+
+
+def bsdf_records(material, iN, N, iT, wow, wiw=None, r0=None, r1=None, distance=None) -> np.ndarray:
+    """(n, 20) float32 records of the BSDF unit entries: {iN, material index (int bits)}, {N, distance}, {iT, r0},
+    {wow, r1}, {wiw, 0}; what a mode does not read may be left out (zeros)."""
+    n = len(iN)
+    rec = np.zeros((n, BSDF_IN_WORDS), np.float32)
+    rec[:, 0:3], rec[:, 4:7], rec[:, 8:11], rec[:, 12:15] = iN, N, iT, wow
+    rec.view(np.int32)[:, 3] = np.asarray(material, np.int32)
+    if wiw is not None:
+        rec[:, 16:19] = wiw
+    for col, v in ((7, distance), (11, r0), (15, r1)):
+        if v is not None:
+            rec[:, col] = v
+    return rec
 
 
 def mat4_identity() -> np.ndarray:

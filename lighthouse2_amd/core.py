@@ -86,6 +86,7 @@ def load_library(path: str | os.PathLike | None = None) -> C.CDLL:
         "lh2_core_filter_buffer": [_P, C.c_int, _P],
         "lh2_core_filter_times": [_P, _F],
         "lh2_core_filter_unit": [_P, C.POINTER(abi.FilterUnit)],
+        "lh2_core_bsdf_unit": [_P, C.POINTER(abi.BsdfUnit)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -374,6 +375,17 @@ class RenderCore:
         if stage == 0:
             return dict(shading=out, motion=motion, moments=moments, features=features)
         return dict(out=out)
+
+    def bsdf_unit(self, sample: bool, records) -> np.ndarray:
+        """The shade kernels' EvaluateBSDF (sample False) or SampleBSDF on abi.bsdf_records, against the materials of
+        set_materials: (n, 8) float32 {value, pdf}, {wiw, specular (uint bits)}."""
+        rec = np.ascontiguousarray(records, np.float32)
+        assert rec.ndim == 2 and rec.shape[1] == abi.BSDF_IN_WORDS
+        out = np.zeros((len(rec), abi.BSDF_OUT_WORDS), np.float32)
+        u = abi.BsdfUnit()
+        u.sample, u.n, u.in_, u.out = int(bool(sample)), len(rec), rec.ctypes.data, out.ctypes.data
+        self._chk(self.lib.lh2_core_bsdf_unit(self.h, C.byref(u)))
+        return out
 
     def scene_info(self) -> dict:
         v = [C.c_int(0) for _ in range(4)]

@@ -184,6 +184,8 @@ void lh2_launch_trace_path( const SceneDev* s, const TraceArgs* a, const ShadePa
 int lh2_path_blocks_per_cu( int waves );
 void lh2_touch_set( uint32_t* bitmap, uint32_t triWord, uint32_t words );   /* LH2_TOUCH builds only (lh2_trace4d.inc) */
 void lh2_launch_spin( unsigned long long ticks, hipStream_t st );
+/* EvaluateBSDF (sample 0) or SampleBSDF on n host-made records (k_bsdf_unit: 5 quads in, 2 out per sample) */
+void lh2_launch_bsdf_unit( const uint4* materials, int materialCount, const float4* in, float4* out, int n, int sample, hipStream_t st );
 void lh2_launch_pack_rows( const float4* acc, float4* dst, int w, int y0, int band, int bandStride, int rows, LaunchEvents ev, hipStream_t st );
 void lh2_launch_unpack_rows( const float4* src, float4* acc, int w, int y0, int band, int bandStride, int rows, LaunchEvents ev, hipStream_t st );
 /* the rows of a band partition (k_pack_rows' mapping); rows 0: every pixel */

@@ -759,6 +759,19 @@ LH2_DEV MatShade mat_shade_load( const SceneDev& s, const TriShade& tq )
 	const uint4* mat = s.materials + (size_t)__float_as_int( tq.t1.w ) * 8;
 	return { mat, mat[0], mat[1] };
 }
+/* the part of GetShadingData that reads the material record's first two quads alone (material_shared.h:52-71): all of it
+   for an untextured material (k_bsdf_unit makes its ShadingData with it) */
+LH2_DEV void material_shading_data( const uint4 baseData, const uint4 params, ShadingData& sd )
+{
+	sd.params = params;
+	sd.color = mk3( h2f( baseData.x & 0xffff ), h2f( baseData.x >> 16 ), h2f( baseData.y & 0xffff ) );
+	sd.flags = 0;
+	sd.transmittance = mk3( h2f( baseData.y >> 16 ), h2f( baseData.z & 0xffff ), h2f( baseData.z >> 16 ) );
+	sd.matID = 0;
+	const v3 tint_xyz = linear_rgb_to_ciexyz( sd.color );
+	const v3 tnt = tint_xyz.y > 0 ? ciexyz_to_linear_rgb( muls( tint_xyz, 1.0f / tint_xyz.y ) ) : s3( 1 );
+	sd.tint = make_float4( tnt.x, tnt.y, tnt.z, tint_xyz.y );
+}
 LH2_DEV void GetShadingData( const SceneDev& s, const v3 D, const float u, const float v, const float coneWidth, const float4* __restrict__ tri,
 	const TriShade& tq, const MatShade& mq, const v3 A, const v3 B, const v3 C, ShadingData& sd, v3& N, v3& iN, v3& fN, v3& T )
 {
@@ -766,15 +779,8 @@ LH2_DEV void GetShadingData( const SceneDev& s, const v3 D, const float u, const
 	const float4 tdata1 = tq.t1, tdata2 = tq.t2, tdata3 = tq.t3, tdata4 = tq.t4, tdata5 = tq.t5, alpha4 = tq.t7;
 	const uint4* mat = mq.mat;
 	const uint4 baseData = mq.m0;
-	sd.params = mq.m1;
-	sd.color = mk3( h2f( baseData.x & 0xffff ), h2f( baseData.x >> 16 ), h2f( baseData.y & 0xffff ) );
-	sd.flags = 0;
-	sd.transmittance = mk3( h2f( baseData.y >> 16 ), h2f( baseData.z & 0xffff ), h2f( baseData.z >> 16 ) );
-	sd.matID = 0;
+	material_shading_data( baseData, mq.m1, sd );
 	const uint32_t flags = baseData.w;
-	const v3 tint_xyz = linear_rgb_to_ciexyz( sd.color );
-	const v3 tnt = tint_xyz.y > 0 ? ciexyz_to_linear_rgb( muls( tint_xyz, 1.0f / tint_xyz.y ) ) : s3( 1 );
-	sd.tint = make_float4( tnt.x, tnt.y, tnt.z, tint_xyz.y );
 	N = iN = fN = mk3( tdata2.w, tdata3.w, tdata4.w );
 	T = xyz( tdata5 );
 	const float w = 1 - (u + v);
@@ -1384,6 +1390,35 @@ LH2_DEV v3 EvaluateBSDF( const ShadingData& sd, const v3 iN, const v3 iT, const 
 		if (clearcoat_pdf > 0) pdf += ww * clearcoat_pdf, value = add3( value, contrib );
 	}
 	return value;
+}
+
+/* the unit entry of the BSDF (lh2_core_bsdf_unit): EvaluateBSDF or SampleBSDF, the functions the shade kernels call, on host
+   records, one per thread.  in: 5 quads per sample {iN, material index}, {N, distance}, {iT, r0}, {wow, r1}, {wiw, -}; out: 2
+   quads {value, pdf}, {wiw, specular}.  ShadingData from the uploaded material record as GetShadingData makes it for an
+   untextured material, with shade_path's faceDir rule for the transmittance (D = -wow); the sampler's wiw and flag start at
+   0 as shade_path's do.  A material index out of range (the host rejects it) leaves its outputs alone */
+__global__ __launch_bounds__( 256 ) void k_bsdf_unit( const uint4* __restrict__ materials, const int materialCount,
+	const float4* __restrict__ in, float4* __restrict__ out, const int n, const int sample )
+{
+	const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+	if (i >= n) return;
+	const float4 a = in[(size_t)i * 5], b = in[(size_t)i * 5 + 1], c = in[(size_t)i * 5 + 2], d = in[(size_t)i * 5 + 3], e = in[(size_t)i * 5 + 4];
+	const int mi = __float_as_int( a.w );
+	if (mi < 0 || mi >= materialCount) return;
+	const uint4* mat = materials + (size_t)mi * 8;
+	ShadingData sd;
+	material_shading_data( mat[0], mat[1], sd );
+	const v3 iN = xyz( a ), N = xyz( b ), iT = xyz( c ), wow = xyz( d );
+	const v3 D = muls( wow, -1.0f );
+	const float faceDir = (dot3( D, N ) > 0) ? -1 : 1;
+	if (faceDir == 1) sd.transmittance = s3( 0 );
+	v3 R = s3( 0 ), value;
+	float pdf = 0;
+	bool specular = false;
+	if (sample) value = SampleBSDF( sd, iN, N, iT, wow, b.w, c.w, d.w, R, pdf, specular );
+	else value = EvaluateBSDF( sd, iN, iT, wow, xyz( e ), pdf );
+	out[(size_t)i * 2] = make_float4( value.x, value.y, value.z, pdf );
+	out[(size_t)i * 2 + 1] = make_float4( R.x, R.y, R.z, __uint_as_float( specular ? 1u : 0u ) );
 }
 
 /* ---- tools --------------------------------------------------------------------------------- */
@@ -2323,6 +2358,11 @@ void lh2_launch_unpack_rows( const float4* src, float4* acc, int w, int y0, int 
 {
 	if (rows * w <= 0) { if (ev.stop) (void)hipEventRecord( ev.stop, st ); return; }
 	LH2_LAUNCH( k_unpack_rows, (rows * w + 255) / 256, 256, st, ev, src, acc, w, y0, band, bandStride, rows );
+}
+void lh2_launch_bsdf_unit( const uint4* materials, int materialCount, const float4* in, float4* out, int n, int sample, hipStream_t st )
+{
+	if (n <= 0) return;
+	LH2_LAUNCH( k_bsdf_unit, (n + 255) / 256, 256, st, LaunchEvents{}, materials, materialCount, in, out, n, sample );
 }
 #ifdef LH2_SHADE_TIMES
 void lh2_shade_times( unsigned long long out[16] ) { (void)hipMemcpyFromSymbol( out, HIP_SYMBOL( lh2_shade_tt ), 16 * 8 ); }

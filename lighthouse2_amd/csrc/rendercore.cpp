@@ -458,6 +458,7 @@ void RenderCore::SetMaterials( const lh2_CoreMaterial* mat, int n )   /* renderc
 		recs[i * 8 + 0].w |= texFlags;
 	}
 	dMaterials.upload( recs.data(), recs.size(), stream );
+	materialCount = n;
 	CHK_HIP( hipStreamSynchronize( stream ) );
 }
 
@@ -1636,6 +1637,28 @@ void RenderCore::FilterUnit( const lh2_FilterUnit& u )
 		lh2_launch_filter_atrous( &aa, {}, stream );
 	}
 	CHK_HIP( hipMemcpyAsync( u.out, out.ptr, sizeof( float4 ) * n, hipMemcpyDeviceToHost, stream ) );
+	CHK_HIP( hipStreamSynchronize( stream ) );
+}
+
+/* EvaluateBSDF / SampleBSDF on host records (lh2_BsdfUnit) against the uploaded materials: upload, one launch, copy back */
+void RenderCore::BsdfUnit( const lh2_BsdfUnit& u )
+{
+	if (u.n < 0 || u.n > (1 << 24) || (u.sample != 0 && u.sample != 1)) FatalError( "bad bsdf unit: sample %d, n %d", u.sample, u.n );
+	if (u.n == 0) return;
+	if (!u.in || !u.out) FatalError( "bsdf unit: null array" );
+	if (materialCount < 1 || !dMaterials.ptr) FatalError( "bsdf unit: no materials (call SetMaterials first)" );
+	for (int i = 0; i < u.n; i++)
+	{
+		const int mi = (int)lh2_f2b( u.in[(size_t)i * 20 + 3] );
+		if (mi < 0 || mi >= materialCount) FatalError( "bsdf unit: sample %d uses material %d of %d", i, mi, materialCount );
+	}
+	DevBuf<float4> in, out;
+	in.upload( (const float4*)u.in, (size_t)u.n * 5, stream );
+	out.resize( (size_t)u.n * 2 );
+	CHK_HIP( hipMemsetAsync( out.ptr, 0, sizeof( float4 ) * 2 * (size_t)u.n, stream ) );
+	lh2_launch_bsdf_unit( dMaterials.ptr, materialCount, in.ptr, out.ptr, u.n, u.sample, stream );
+	CHK_HIP( hipGetLastError() );
+	CHK_HIP( hipMemcpyAsync( u.out, out.ptr, sizeof( float4 ) * 2 * (size_t)u.n, hipMemcpyDeviceToHost, stream ) );
 	CHK_HIP( hipStreamSynchronize( stream ) );
 }
 

@@ -261,6 +261,7 @@ public:
 	void GetFilterBuffer( int which, void* hostOut );
 	void GetFilterTimes( float* ms4 );
 	void FilterUnit( const lh2_FilterUnit& u );
+	void BsdfUnit( const lh2_BsdfUnit& u );
 	void SetFilterAllowed( bool on );    /* MultiDevice: a band has no neighbours across its edge, so no core of it filters */
 	bool FilterOn() const { return filterOn && filterAllowed; }
 	/* in-process multi-device gather (multidevice.cpp): rows packed by the core of rank `rank` of a
@@ -405,6 +406,7 @@ private:
 	hipGraphicsResource_t glResource = nullptr;   /* registered GL_RGBA32F target texture */
 	uint32_t glTexture = 0;
 	DevBuf<uint4> dMaterials;
+	int materialCount = 0;               /* the records SetMaterials uploaded (BsdfUnit checks its indices against it) */
 	std::vector<lh2_CoreTexDesc> texDescs;   /* copies, firstPixel assigned per storage (rendercore.cpp:276-292) */
 	DevBuf<uint32_t> dArgb32, dNrm32;        /* continuous texel arrays (rendercore.cpp:299-336) */
 	DevBuf<float4> dArgb128;

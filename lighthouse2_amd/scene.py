@@ -204,6 +204,7 @@ class Scene:
     textures: list = dataclasses.field(default_factory=list)   # Texture
     view: abi.ViewPyramid | None = None
     name: str = "scene"
+    featured: dict = dataclasses.field(default_factory=dict)   # disney_scene: material index -> its parameters
 
     @property
     def tri_count(self) -> int:
@@ -552,6 +553,81 @@ def animate_instances(sc: Scene, frame: int, seed: int = 7) -> None:
         M[:, 3] = T[:, 3]
         new.append((mesh, M.astype(np.float32)))
     sc.instances = new
+
+
+# ---------------------------------------------------------------------------------------------
+# every lobe of the Disney BSDF: one smooth sphere and one flat patch per material
+# ---------------------------------------------------------------------------------------------
+DISNEY_PARAMS = ("metallic", "subsurface", "specular", "roughness", "specularTint", "anisotropic", "sheen", "sheenTint",
+                 "clearcoat", "clearcoatGloss", "transmission")
+# (name, colour, the parameters the material is about, extras): the remaining parameters get small distinct bytes
+# (disney_materials), so that all eleven bytes of a material differ and a swapped byte lane changes it
+_DISNEY = [
+    ("sheen", (0.05, 0.12, 0.55), dict(roughness=0.8, specular=0.1, sheen=1.0, sheenTint=0.9), {}),
+    ("clearcoat", (0.7, 0.08, 0.1), dict(roughness=0.6, specular=0.3, clearcoat=1.0, clearcoatGloss=0.8), {}),
+    ("anisotropic", (0.9, 0.55, 0.15), dict(roughness=0.35, specular=0.5, metallic=0.9, anisotropic=0.95), {}),
+    ("subsurface", (0.15, 0.7, 0.25), dict(roughness=0.7, specular=0.2, subsurface=0.9), {}),
+    ("specularTint", (0.01, 0.03, 0.35), dict(roughness=0.3, specular=1.0, specularTint=0.97), {}),
+    ("all", (0.6, 0.12, 0.45), dict(metallic=0.25, subsurface=0.55, specular=0.85, roughness=0.45, specularTint=0.95, anisotropic=0.7,
+                                     sheen=1.0, sheenTint=0.9, clearcoat=0.8, clearcoatGloss=0.65, transmission=0.3),
+     dict(eta=1.4, absorption=(0.2, 0.6, 0.1))),
+    ("half-glass", (0.9, 0.92, 0.95), dict(roughness=0.4, specular=0.6, transmission=0.5), dict(eta=1.5, absorption=(0.9, 0.3, 0.1))),
+    ("black", (0.0, 0.0, 0.0), {}, {}),
+]
+
+
+def disney_materials() -> tuple[list, dict]:
+    """The materials of disney_scene and, per material index, the parameters it is about.  Every other parameter of a
+    material (the black one apart: all its lobe weights are zero) is a small value whose byte, 0 .. 10, differs from
+    every other byte of the material."""
+    mats = [abi.make_material((0.7, 0.7, 0.65), roughness=1.0),       # 0 floor
+            abi.make_material((0.3, 0.4, 0.7), roughness=1.0)]        # 1 wall
+    featured = {}
+    for name, color, par, extra in _DISNEY:
+        kw = dict(par)
+        if par:
+            used = {int(np.float32(v) * np.float32(255.0)) for v in par.values()}
+            fill = (b for b in range(0, 64) if b not in used)
+            for p in DISNEY_PARAMS:
+                if p not in kw:
+                    kw[p] = (next(fill) + 0.5) / 255.0
+            kw.setdefault("eta", 1.45)
+        kw.update(extra)
+        featured[len(mats)] = dict(par)
+        mats.append(abi.make_material(color, **kw))
+    return mats, featured
+
+
+def disney_scene(width: int = 160, height: int = 96) -> Scene:
+    """A scene that reaches every lobe of the Disney BSDF: per material of disney_materials one smooth-shaded sphere
+    (vertex normals, so the interpolated normal differs from the face's) and one flat patch, in a 4 x 2 grid over a floor
+    and in front of a wall; an area light and a point light (NEE evaluates the BSDF), the gradient sky.  Scene.featured
+    maps a material index to the parameters that material is about."""
+    mats, featured = disney_materials()
+    light_mat = len(mats)
+    mats.append(abi.make_material((12.0, 12.0, 11.0)))
+    V0, V1, V2, M = [], [], [], []
+    for o, du, dv, nu, nv, mat in (((-8, -2.9, -2), (16, 0, 0), (0, 0, 12), 8, 6, 0), ((-8, -2.9, -1.5), (0, 8, 0), (16, 0, 0), 4, 8, 1)):
+        a, b, c = _grid_quads(o, du, dv, nu, nv)
+        V0.append(a), V1.append(b), V2.append(c), M.append(np.full(len(a), mat, np.uint32))
+    parts = [abi.tris_from_vertices(np.concatenate(V0), np.concatenate(V1), np.concatenate(V2), np.concatenate(M))]
+    for k, mat in enumerate(sorted(featured)):
+        x, y = -3.6 + 2.4 * (k % 4), 1.75 - 2.6 * (k // 4)
+        a, b, c, vn = _sphere((x, y, 0.0), 0.75, 24, 12)
+        parts.append(abi.tris_from_vertices(a, b, c, np.full(len(a), mat, np.uint32), vertex_normals=vn))
+        parts.append(quad_tris((0, 0.5, 1), (x, y - 1.1, 0.3), 1.3, 0.55, mat))
+    tris = np.concatenate(parts)
+    q = quad_tris((0, -1, 0), (0, 4.3, 3.0), 6, 2, light_mat)
+    q.view(np.int32)[:, abi.TRI["ltriIdx"]] = [0, 1]
+    base = len(tris)
+    tris = np.concatenate([tris, q])
+    sc = Scene(meshes=[tris], instances=[(0, np.eye(4, dtype=np.float32))], materials=mats,
+               area_lights=[light_from_tri(tris[base + i], base + i, 0, (12.0, 12.0, 11.0)) for i in range(2)],
+               point_lights=[point_light((-4.0, 2.0, 6.0), (30.0, 28.0, 25.0), energy=83.0)], name="disney")
+    sc.featured = featured
+    sc.sky = gradient_sky(64, 32)
+    sc.view = camera_view((0, 0.3, 9), (0, 0, -1), fov_deg=40, aspect=width / height, focal=5, pixel_height=height)
+    return sc
 
 
 # ---------------------------------------------------------------------------------------------

@@ -83,6 +83,9 @@ def lib() -> C.CDLL:
         L.orc_random_barycentrics.restype = None
         L.orc_random_point_on_light.argtypes = [_P, C.c_float, C.c_float, _F, _F, _F]
         L.orc_random_point_on_light.restype = None
+        for k in ("orc_evaluate_bsdf", "orc_sample_bsdf"):
+            getattr(L, k).argtypes = [_P, C.c_int, _F, _F]
+            getattr(L, k).restype = C.c_int
         _lib = L
     return _lib
 
@@ -239,6 +242,17 @@ class Oracle:
         vis = np.zeros((n, 2), np.uint32) if visits else None
         self.L.orc_trace_closest(self.o, _fp(o), _fp(d), n, _up(hits), _up(vis) if visits else None, self.threads)
         return (hits, vis) if visits else hits
+
+    def bsdf_unit(self, sample: bool, records):
+        """EvaluateBSDF (sample False) or SampleBSDF on abi.bsdf_records against the materials of set_materials:
+        (n, 8) float32 {value, pdf}, {wiw, specular (uint bits)}, as RenderCore.bsdf_unit."""
+        rec = np.ascontiguousarray(records, np.float32)
+        assert rec.ndim == 2 and rec.shape[1] == abi.BSDF_IN_WORDS
+        out = np.zeros((len(rec), abi.BSDF_OUT_WORDS), np.float32)
+        fn = self.L.orc_sample_bsdf if sample else self.L.orc_evaluate_bsdf
+        if fn(self.o, len(rec), _fp(rec), _fp(out)) != 0:
+            raise ValueError("bsdf_unit: material index out of range")
+        return out
 
     def trace_any(self, org, dirs):
         o = np.ascontiguousarray(org, np.float32)

@@ -17,6 +17,11 @@
      Q6 blue-noise rank lookups past the end of the table read zero padding.
      Q5 light potentials are recomputed instead of stored in a MAXISLIGHTS=8 array, which the
         reference overruns for > 8 lights; values are identical for <= 8 lights.
+   Kept as the reference's text has them (tests/bsdf_ref.py):
+     Q10 EvaluateBSDF's sheen value replaces the diffuse value (one out-parameter, disney.h:315-316).
+     Q11 evaluate_sheen's half vector is normalize( wow + wow ).
+     Q12 a material with four zero lobe weights has NaN weights and pdf 0.
+     Q13 SampleBSDF's contrib keeps the previous lobe's value when a microfacet evaluation exits early.
 */
 #include "pt_oracle.h"
 #include "../include/lh2_detmath.h"
@@ -872,10 +877,10 @@ int orc_fetch_texel( const Oracle* o, int storage, float u, float v, int offset,
 	return 0;
 }
 
-static void GetShadingData( const Oracle* o, f3 D, float u, float v, float coneWidth, const lh2_CoreTri* tri, int instIdx,
-	ShadingData* sd, f3* N, f3* iN, f3* fN, f3* T )
+/* the part of GetShadingData that reads the material record alone (material_shared.h:52-71): all of it for an untextured
+   material */
+static void MaterialShadingData( const Mat* mat, ShadingData* sd )
 {
-	const Mat* mat = &o->mats[tri->material];
 	sd->color = mk3( lh2_h2f( mat->diffuse[0] ), lh2_h2f( mat->diffuse[1] ), lh2_h2f( mat->diffuse[2] ) );
 	sd->flags = 0;
 	sd->transmittance = mk3( lh2_h2f( mat->transmittance[0] ), lh2_h2f( mat->transmittance[1] ), lh2_h2f( mat->transmittance[2] ) );
@@ -884,6 +889,12 @@ static void GetShadingData( const Oracle* o, f3 D, float u, float v, float coneW
 	const f3 tint_xyz = linear_rgb_to_ciexyz( sd->color );
 	const f3 tnt = tint_xyz.y > 0 ? ciexyz_to_linear_rgb( muls( tint_xyz, 1.0f / tint_xyz.y ) ) : s3( 1 );
 	sd->tint.x = tnt.x, sd->tint.y = tnt.y, sd->tint.z = tnt.z, sd->tint.w = tint_xyz.y;
+}
+static void GetShadingData( const Oracle* o, f3 D, float u, float v, float coneWidth, const lh2_CoreTri* tri, int instIdx,
+	ShadingData* sd, f3* N, f3* iN, f3* fN, f3* T )
+{
+	const Mat* mat = &o->mats[tri->material];
+	MaterialShadingData( mat, sd );
 	const uint32_t flags = mat->flags;
 	*N = *iN = *fN = mk3( tri->Nx, tri->Ny, tri->Nz );
 	*T = lf3( tri->T );
@@ -1477,6 +1488,39 @@ static f3 EvaluateBSDF( const ShadingData* sd, f3 iN, f3 iT, f3 wow, f3 wiw, flo
 	}
 	return value;
 }
+
+/* unit entries: EvaluateBSDF / SampleBSDF on host records against the materials of orc_set_materials (so the packing of
+   orc_set_materials and the unpacking of GetShadingData are part of what runs).  Per sample 20 floats in: {iN, material
+   index (int bits)}, {N, distance}, {iT, r0}, {wow, r1}, {wiw, -}; 8 out: {value, pdf}, {wiw, specular (0 / 1, uint bits)}.
+   ShadingData as GetShadingData makes it for an untextured material, with shade_one's faceDir rule for the transmittance
+   (D = -wow).  The sampler's wiw and specular flag start at 0, as shade_one's do. */
+static int bsdf_unit( const Oracle* o, int sample, int n, const float* in20, float* out8 )
+{
+	for (int i = 0; i < n; i++)
+	{
+		const float* r = in20 + (size_t)i * 20;
+		float* w = out8 + (size_t)i * 8;
+		const int mi = (int)fbits( r[3] );
+		if (mi < 0 || mi >= o->matCount) return -1;
+		const f3 iN = mk3( r[0], r[1], r[2] ), N = mk3( r[4], r[5], r[6] ), iT = mk3( r[8], r[9], r[10] );
+		const f3 wow = mk3( r[12], r[13], r[14] ), wiw = mk3( r[16], r[17], r[18] );
+		ShadingData sdv, *sd = &sdv;
+		MaterialShadingData( &o->mats[mi], sd );
+		const f3 D = muls( wow, -1.0f );
+		const float faceDir = (dot3( D, N ) > 0) ? -1 : 1;
+		if (faceDir == 1) sd->transmittance = s3( 0 );
+		f3 value, R = s3( 0 );
+		float pdf = 0;
+		int specular = 0;
+		if (sample) value = SampleBSDF( sd, iN, N, iT, wow, r[7], r[11], r[15], &R, &pdf, &specular );
+		else value = EvaluateBSDF( sd, iN, iT, wow, wiw, &pdf );
+		w[0] = value.x, w[1] = value.y, w[2] = value.z, w[3] = pdf;
+		w[4] = R.x, w[5] = R.y, w[6] = R.z, w[7] = bitsf( (uint32_t)specular );
+	}
+	return 0;
+}
+int orc_evaluate_bsdf( const Oracle* o, int n, const float* in20, float* out8 ) { return bsdf_unit( o, 0, n, in20, out8 ); }
+int orc_sample_bsdf( const Oracle* o, int n, const float* in20, float* out8 ) { return bsdf_unit( o, 1, n, in20, out8 ); }
 
 /* ------------------------------------------------------------------------------------- */
 /* camera: kernels/camera.h:22-94                                                          */

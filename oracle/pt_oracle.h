@@ -75,6 +75,12 @@ float orc_light_pick_prob( const Oracle* o, int idx, const float* O3, const floa
 void orc_random_barycentrics( float r0, float* out3 );
 void orc_random_point_on_light( const Oracle* o, float r0, float r1, const float* I3, const float* N3, float* out8 );
 
+/* the Disney BSDF (disney.h EvaluateBSDF / SampleBSDF) on host records against the materials of orc_set_materials.  Per
+   sample 20 floats in: {iN, material index (int bits)}, {N, distance}, {iT, r0}, {wow, r1}, {wiw, -}; 8 out: {value, pdf},
+   {wiw, specular (0 / 1, uint bits)}.  Returns -1 for a material index out of range */
+int orc_evaluate_bsdf( const Oracle* o, int n, const float* in20, float* out8 );
+int orc_sample_bsdf( const Oracle* o, int n, const float* in20, float* out8 );
+
 /* numerics KATs */
 uint32_t orc_wanghash( uint32_t s );
 uint32_t orc_xorshift( uint32_t s );
