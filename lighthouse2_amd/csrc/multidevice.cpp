@@ -154,7 +154,8 @@ void MultiDevice::SetLights( const lh2_CoreLightTri* a, int na, const lh2_CorePo
 }
 void MultiDevice::SetSkyData( const float* px, uint32_t w, uint32_t h ) { ForEach( [&]( int i ) { cores[i]->SetSkyData( px, w, h ); } ); }
 /* one BLAS build per mesh, not one per device: core 0 takes the mesh (a CPU build is deferred), the other
-   sub-cores upload its shading triangles and share core 0's deferred build (RenderCore::AdoptGeometry) */
+   sub-cores upload its shading triangles and share core 0's deferred build (SceneAccel::AdoptGeometry, which compares the
+   build's recorded BuildSettings with the sub-core's own; Setting keeps them equal) */
 void MultiDevice::SetGeometry( int meshIdx, const float* v, int vc, int tc, const lh2_CoreTri* t, const uint32_t* alpha )
 {
 	cores[0]->SetGeometry( meshIdx, v, vc, tc, t, alpha );

@@ -23,9 +23,6 @@
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
-#include <atomic>
-#include <functional>
-#include <thread>
 
 #include "../../include/lh2_detmath.h"
 #include "lh2_device.h"
@@ -42,8 +39,6 @@ void FatalError( const char* fmt, ... )
 	throw std::runtime_error( buf );
 }
 
-#define CHK_HIP( stmt ) do { hipError_t e_ = (stmt); if (e_ != hipSuccess) FatalError( "%s failed: %s (%s:%d)", #stmt, hipGetErrorString( e_ ), __FILE__, __LINE__ ); } while (0)
-
 static std::string LibraryDir()
 {
 	Dl_info info;
@@ -54,31 +49,6 @@ static std::string LibraryDir()
 		return s == std::string::npos ? std::string( "." ) : p.substr( 0, s );
 	}
 	return ".";
-}
-
-/* mat4::Inverted (RenderSystem/common_types.h:586-628); same formula as the oracle */
-static void Mat4Inverse( const float* c, float* out )
-{
-	const float inv[16] = {
-		c[5] * c[10] * c[15] - c[5] * c[11] * c[14] - c[9] * c[6] * c[15] + c[9] * c[7] * c[14] + c[13] * c[6] * c[11] - c[13] * c[7] * c[10],
-		-c[1] * c[10] * c[15] + c[1] * c[11] * c[14] + c[9] * c[2] * c[15] - c[9] * c[3] * c[14] - c[13] * c[2] * c[11] + c[13] * c[3] * c[10],
-		c[1] * c[6] * c[15] - c[1] * c[7] * c[14] - c[5] * c[2] * c[15] + c[5] * c[3] * c[14] + c[13] * c[2] * c[7] - c[13] * c[3] * c[6],
-		-c[1] * c[6] * c[11] + c[1] * c[7] * c[10] + c[5] * c[2] * c[11] - c[5] * c[3] * c[10] - c[9] * c[2] * c[7] + c[9] * c[3] * c[6],
-		-c[4] * c[10] * c[15] + c[4] * c[11] * c[14] + c[8] * c[6] * c[15] - c[8] * c[7] * c[14] - c[12] * c[6] * c[11] + c[12] * c[7] * c[10],
-		c[0] * c[10] * c[15] - c[0] * c[11] * c[14] - c[8] * c[2] * c[15] + c[8] * c[3] * c[14] + c[12] * c[2] * c[11] - c[12] * c[3] * c[10],
-		-c[0] * c[6] * c[15] + c[0] * c[7] * c[14] + c[4] * c[2] * c[15] - c[4] * c[3] * c[14] - c[12] * c[2] * c[7] + c[12] * c[3] * c[6],
-		c[0] * c[6] * c[11] - c[0] * c[7] * c[10] - c[4] * c[2] * c[11] + c[4] * c[3] * c[10] + c[8] * c[2] * c[7] - c[8] * c[3] * c[6],
-		c[4] * c[9] * c[15] - c[4] * c[11] * c[13] - c[8] * c[5] * c[15] + c[8] * c[7] * c[13] + c[12] * c[5] * c[11] - c[12] * c[7] * c[9],
-		-c[0] * c[9] * c[15] + c[0] * c[11] * c[13] + c[8] * c[1] * c[15] - c[8] * c[3] * c[13] - c[12] * c[1] * c[11] + c[12] * c[3] * c[9],
-		c[0] * c[5] * c[15] - c[0] * c[7] * c[13] - c[4] * c[1] * c[15] + c[4] * c[3] * c[13] + c[12] * c[1] * c[7] - c[12] * c[3] * c[5],
-		-c[0] * c[5] * c[11] + c[0] * c[7] * c[9] + c[4] * c[1] * c[11] - c[4] * c[3] * c[9] - c[8] * c[1] * c[7] + c[8] * c[3] * c[5],
-		-c[4] * c[9] * c[14] + c[4] * c[10] * c[13] + c[8] * c[5] * c[14] - c[8] * c[6] * c[13] - c[12] * c[5] * c[10] + c[12] * c[6] * c[9],
-		c[0] * c[9] * c[14] - c[0] * c[10] * c[13] - c[8] * c[1] * c[14] + c[8] * c[2] * c[13] + c[12] * c[1] * c[10] - c[12] * c[2] * c[9],
-		-c[0] * c[5] * c[14] + c[0] * c[6] * c[13] + c[4] * c[1] * c[14] - c[4] * c[2] * c[13] - c[12] * c[1] * c[6] + c[12] * c[2] * c[5],
-		c[0] * c[5] * c[10] - c[0] * c[6] * c[9] - c[4] * c[1] * c[10] + c[4] * c[2] * c[9] + c[8] * c[1] * c[6] - c[8] * c[2] * c[5] };
-	const float det = c[0] * inv[0] + c[1] * inv[4] + c[2] * inv[8] + c[3] * inv[12];
-	if (det != 0) { const float invdet = 1.0f / det; for (int i = 0; i < 16; i++) out[i] = inv[i] * invdet; }
-	else for (int i = 0; i < 16; i++) out[i] = (i % 5 == 0) ? 1.0f : 0.0f;
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -142,18 +112,7 @@ void RenderCore::Init()   /* rendercore.cpp:96-143 */
 	CHK_HIP( hipHostMalloc( (void**)&hostStats, sizeof( FrameStats ), hipHostMallocCoherent ) );   /* written by k_finalize (system scope) */
 	memset( hostStats, 0, sizeof( FrameStats ) );
 	for (auto& e : evFrame) CHK_HIP( hipEventCreate( &e ) );
-	for (auto& e : evStage) CHK_HIP( hipEventCreateWithFlags( &e, hipEventDisableTiming ) );
-	dSceneError.resize( 2 ), dTlasDepth.resize( 1 ), dBlasQError.resize( 1 );
-	CHK_HIP( hipMemsetAsync( dSceneError.ptr, 0, sizeof( int ) * 2, stream ) );
-	CHK_HIP( hipEventCreateWithFlags( &evTlasReady, hipEventDisableTiming ) );
-	for (auto& e : evTlasFree) CHK_HIP( hipEventCreateWithFlags( &e, hipEventDisableTiming ) );
-	CHK_HIP( hipMemsetAsync( dTlasDepth.ptr, 0, sizeof( int ), stream ) );
-	CHK_HIP( hipMemsetAsync( dBlasQError.ptr, 0, sizeof( int ), stream ) );
-	for (auto& d : dInstDesc)   /* shading reads record 0 for a miss (HitInstance): it always exists */
-	{
-		d.resize( 1 );
-		CHK_HIP( hipMemsetAsync( d.ptr, 0, sizeof( lh2_CoreInstanceDesc ), stream ) );
-	}
+	accel.Init( stream, aheadStream );
 	CHK_HIP( hipStreamSynchronize( stream ) );
 	initialized = true;
 }
@@ -192,13 +151,12 @@ void RenderCore::SetInteropTexture( uint32_t glTextureId )
 bool RenderCore::UsePackets() const
 {
 	if (packetPrimary >= 0) return packetPrimary != 0;
-	const double bytes = ((double)blasNodeCount + tlasCapacity) * 64.0 + (double)blasTriCount * 48.0;
-	return bytes <= kPacketMaxBytes;
+	return accel.Bytes() <= kPacketMaxBytes;
 }
 
 /* traversal loop of the per-ray launches (setting "traceVersion"): 7, the BVH4 loop (lh2_trace4d.inc), unless
    the BVH4 is not built (setting "bvh4" 0) or the reference BVH2 loop is asked for (1) */
-int RenderCore::TraceVersion() const { return (traceVersion == 1 || !bvh4) ? 1 : 7; }
+int RenderCore::TraceVersion() const { return (traceVersion == 1 || !accel.build.bvh4) ? 1 : 7; }
 
 void RenderCore::EnsureBuffers()
 {
@@ -280,15 +238,15 @@ void RenderCore::Setting( const char* name, float value )  /* rendercore.cpp:439
 	/* traversal: test parked BLAS leaves once this many lanes of a wave hold one (0 = every step) */
 	else if (!strcmp( name, "leafBatch" )) leafBatch = std::min( 64, std::max( 0, (int)value ) );
 	/* BLAS build parameters, used by later SetGeometry calls */
-	else if (!strcmp( name, "bvhMaxLeaf" )) bvhMaxLeaf = std::min( 16, std::max( 1, (int)value ) );
-	else if (!strcmp( name, "bvhSpatial" )) bvhSpatial = std::max( 0.0f, value );   /* SBVH overlap threshold (x root area); 0: off */
-	else if (!strcmp( name, "bvhSpatialBudget" )) bvhSpatialBudget = std::min( 4.0f, std::max( 0.0f, value ) );
-	else if (!strcmp( name, "bvhSpatialMinRefs" )) bvhSpatialMinRefs = std::max( 0, (int)value );
-	else if (!strcmp( name, "bvh4Collapse" )) bvh4Collapse = value != 0;
-	else if (!strcmp( name, "bvh4" )) { bvh4 = value != 0; }   /* before SetGeometry */
-	else if (!strcmp( name, "gpuBuild" )) gpuBuild = value != 0;          /* BLAS builder of later SetGeometry calls */
-	else if (!strcmp( name, "buildThreads" )) buildThreads = std::max( 0, (int)value );   /* host threads of the deferred CPU builds */
-	else if (!strcmp( name, "gpuTlas" )) { gpuTlas = value != 0; instancesDirty = true; }
+	else if (!strcmp( name, "bvhMaxLeaf" )) accel.build.maxLeaf = std::min( 16, std::max( 1, (int)value ) );
+	else if (!strcmp( name, "bvhSpatial" )) accel.build.spatial = std::max( 0.0f, value );   /* SBVH overlap threshold (x root area); 0: off */
+	else if (!strcmp( name, "bvhSpatialBudget" )) accel.build.spatialBudget = std::min( 4.0f, std::max( 0.0f, value ) );
+	else if (!strcmp( name, "bvhSpatialMinRefs" )) accel.build.spatialMinRefs = std::max( 0, (int)value );
+	else if (!strcmp( name, "bvh4Collapse" )) accel.build.bvh4Collapse = value != 0;
+	else if (!strcmp( name, "bvh4" )) accel.build.bvh4 = value != 0;   /* before SetGeometry */
+	else if (!strcmp( name, "gpuBuild" )) accel.gpuBuild = value != 0;          /* BLAS builder of later SetGeometry calls */
+	else if (!strcmp( name, "buildThreads" )) accel.buildThreads = std::max( 0, (int)value );   /* host threads of the deferred CPU builds */
+	else if (!strcmp( name, "gpuTlas" )) { accel.gpuTlas = value != 0; accel.InstancesChanged(); }
 	else if (!strcmp( name, "chordSplit" )) chordSplit = std::max( 0.0f, value );   /* two-ended path segments (longest first); 0: off */
 	else if (!strcmp( name, "packetHeavy" )) packetHeavy = value < 0 ? -1.0f : value;   /* heavy-first primary packets; 0: off; -1: by frame */
 	else if (!strcmp( name, "pathTail" )) pathTail = std::max( 0, (int)value );   /* bounces from this one in one trace-and-shade launch; 0: off */
@@ -360,11 +318,12 @@ void RenderCore::Setting( const char* name, float value )  /* rendercore.cpp:439
 /* the current value of a setting (extension: the reference has no getter); false for unknown names */
 bool RenderCore::GetSetting( const char* name, float& value ) const
 {
+	const BuildSettings& bs = accel.build;
 	struct { const char* n; float v; } t[] = {
 		{ "epsilon", geometryEpsilon }, { "clampValue", clampValue }, { "maxPathLength", (float)maxPathLength },
 		{ "primeRef", (float)primeRef }, { "tiledRays", (float)tiledRays }, { "refill", (float)refillOther }, { "leafBatch", (float)leafBatch },
-		{ "bvhMaxLeaf", (float)bvhMaxLeaf }, { "bvhSpatial", bvhSpatial }, { "bvhSpatialBudget", bvhSpatialBudget }, { "bvhSpatialMinRefs", (float)bvhSpatialMinRefs },
-		{ "bvh4Collapse", (float)bvh4Collapse }, { "bvh4", (float)bvh4 }, { "gpuBuild", (float)gpuBuild }, { "buildThreads", (float)buildThreads }, { "gpuTlas", (float)gpuTlas },
+		{ "bvhMaxLeaf", (float)bs.maxLeaf }, { "bvhSpatial", bs.spatial }, { "bvhSpatialBudget", bs.spatialBudget }, { "bvhSpatialMinRefs", (float)bs.spatialMinRefs },
+		{ "bvh4Collapse", (float)bs.bvh4Collapse }, { "bvh4", (float)bs.bvh4 }, { "gpuBuild", (float)accel.gpuBuild }, { "buildThreads", (float)accel.buildThreads }, { "gpuTlas", (float)accel.gpuTlas },
 		{ "chordSplit", chordSplit }, { "packetHeavy", packetHeavy }, { "pathTail", (float)pathTail }, { "pathTailBatch", (float)pathTailBatch },
 		{ "shadowOverlap", (float)shadowOverlap }, { "cameraFused", (float)cameraFused }, { "frameOverlap", (float)frameOverlap }, { "earlyShade", (float)earlyShade },
 		{ "sideBlocks", (float)sideBlocks }, { "pathTailBlocks", (float)pathTailBlocks }, { "shadeBlocks", (float)shadeBlocks }, { "finalShadowBlocks", (float)finalShadowBlocks },
@@ -481,190 +440,20 @@ void RenderCore::SetSkyData( const float* pixels, uint32_t width, uint32_t heigh
 	CHK_HIP( hipStreamSynchronize( stream ) );
 }
 
-static std::atomic<int> gBlasBuilds{ 0 };
-int RenderCore::BlasBuildCount() { return gBlasBuilds.load(); }
-void HostBlas::Run( int threads )
-{
-	std::call_once( once, [&] { job( *this, threads ); job = nullptr; gBlasBuilds++; } );
-}
-
+/* the scene calls go to the SceneAccel (scene_accel.cpp); what stays here is sceneVersion: new device-resident scene data,
+   so the next fused frame's primary launch waits for the previous frame.  An instance-only UpdateToplevel leaves it alone
+   (it writes the TLAS slot no frame in flight reads), so the next frame may still overlap */
 void RenderCore::SetGeometry( int meshIdx, const float*, int, int triangleCount, const lh2_CoreTri* tris, const uint32_t* )
 {
 	sceneVersion++;
-	/* rendercore.cpp:215-223 + core_mesh.cpp:36-67: meshes arrive first-time in sequential order */
-	if (meshIdx < 0 || meshIdx > (int)meshes.size()) FatalError( "SetGeometry: mesh index %d out of sequence", meshIdx );
-	if (meshIdx == (int)meshes.size()) meshes.push_back( new CoreMeshHost() );
-	CoreMeshHost& m = *meshes[meshIdx];
-	m.build = nullptr;   /* a build of earlier data not run yet is superseded */
-	const auto t0 = std::chrono::high_resolution_clock::now();
-	m.triCount = triangleCount;
-	m.shadeTris.upload( (const float4*)tris, (size_t)triangleCount * 11, stream );
-	m.shadeTris.resize( 11 );
-	bool cpuBuild = !(gpuBuild && triangleCount >= 2);
-	if (!cpuBuild)
-	{
-		/* GPU PLOC build straight from the uploaded CoreTri records (bvh_gpu.h) */
-		float4 *nodes = nullptr, *tris48 = nullptr;
-		GpuBuildResult r;
-		SyncTlas();   /* a TLAS build queued on the ahead stream uses the same builder scratch: this build follows it */
-		gpuBvh.BuildBlas( m.shadeTris.ptr, triangleCount, bvhMaxLeaf, 1.0f, &nodes, &tris48, r, stream );
-		m.bvhNodes.adopt( nodes, (size_t)r.nodeCount * 4 );
-		m.bvhTris.adopt( tris48, (size_t)triangleCount * 3 );
-		m.leafTris = triangleCount;
-		m.nodeCount = r.nodeCount, m.maxDepth = r.maxDepth;
-		for (int k = 0; k < 3; k++) m.aabbLo[k] = r.lo[k], m.aabbHi[k] = r.hi[k];
-		/* pathological inputs (e.g. long runs of nearly coincident triangles) can make a clustered tree
-		   deep; the top-down SAH build bounds the depth by splitting such ranges in the middle */
-		if (r.maxDepth > LH2_STACK_TOTAL / 2) cpuBuild = true;
-	}
-	if (cpuBuild)
-	{
-		/* CPU binned-SAH build (bvh_build.cpp), deferred: the inputs are copied now (the caller's triangle
-		   array is borrowed for this call only) and the builds of all meshes set since the last one run in
-		   parallel over the meshes when the scene is first needed (FlushBuilds) */
-		std::vector<Aabb> prims( triangleCount );
-		std::vector<float> verts( (size_t)triangleCount * 9 );
-		for (int k = 0; k < 3; k++) m.aabbLo[k] = 1e30f, m.aabbHi[k] = -1e30f;
-		for (int i = 0; i < triangleCount; i++)
-		{
-			const lh2_CoreTri& t = tris[i];
-			const float v[9] = { t.vertex0.x, t.vertex0.y, t.vertex0.z, t.vertex1.x, t.vertex1.y, t.vertex1.z, t.vertex2.x, t.vertex2.y, t.vertex2.z };
-			memcpy( &verts[(size_t)i * 9], v, sizeof( v ) );
-			for (int k = 0; k < 3; k++)
-			{
-				prims[i].lo[k] = std::min( std::min( v[k], v[3 + k] ), v[6 + k] );
-				prims[i].hi[k] = std::max( std::max( v[k], v[3 + k] ), v[6 + k] );
-				m.aabbLo[k] = std::min( m.aabbLo[k], prims[i].lo[k] ), m.aabbHi[k] = std::max( m.aabbHi[k], prims[i].hi[k] );
-			}
-		}
-		const int maxLeaf = bvhMaxLeaf, collapse = bvh4Collapse, wide = bvh4;
-		const float cost = 1.0f, spatial = bvhSpatial, budget = bvhSpatialBudget;
-		const int minRefs = bvhSpatialMinRefs;
-		m.build = std::make_shared<HostBlas>();
-		m.build->job = [prims = std::move( prims ), verts = std::move( verts ), maxLeaf, collapse, wide, cost, spatial, budget, minRefs]( HostBlas& r, int threads ) {
-			BvhOutput bvh;
-			BuildBvh2( prims, maxLeaf, threads, bvh, cost, 0, spatial > 0 ? verts.data() : nullptr, spatial, budget, minRefs );
-			/* one triangle record per leaf slot (a spatial split can reference a triangle from several leaves):
-			   v0, e1 = v1 - v0, e2 = v2 - v0 in fp32, exactly as the oracle's intersect_tri */
-			std::vector<float>& t48 = r.tris48;
-			t48.assign( std::max<size_t>( bvh.perm.size(), 1 ) * 12, 0.0f );
-			for (size_t j = 0; j < bvh.perm.size(); j++)
-			{
-				const uint32_t ti = bvh.perm[j];
-				const float* v = &verts[(size_t)ti * 9];
-				float* o = &t48[j * 12];
-				o[0] = v[0], o[1] = v[1], o[2] = v[2]; memcpy( &o[3], &ti, 4 );
-				o[4] = v[3] - v[0], o[5] = v[4] - v[1], o[6] = v[5] - v[2], o[7] = 0;
-				o[8] = v[6] - v[0], o[9] = v[7] - v[1], o[10] = v[8] - v[2], o[11] = 0;
-			}
-			r.leafTris = (int)bvh.perm.size();
-			r.nodeCount = (int)(bvh.nodes.size() / 16), r.maxDepth = bvh.maxDepth;
-			r.nodes4.clear(), r.depth4 = 0;
-			/* BVH4 collapse: dynamic programming (surface-area costs: node step 1, leaf visit 0.4, triangle test 0.5,
-			   one triangle per leaf; merged leaves run the leaf loop divergent: slower, r02s) or greedy */
-			if (wide) r.depth4 = collapse ? CollapseBvh4Sah( bvh.nodes.data(), (size_t)r.nodeCount, r.nodes4, 0.4f, 0.5f, 1 )
-				: CollapseBvh4( bvh.nodes.data(), (size_t)r.nodeCount, r.nodes4 );
-			r.nodes2 = std::move( bvh.nodes );
-		};
-		pendingBuilds = true;
-	}
-	else if (bvh4)
-	{
-		/* GPU-built BLAS: collapse on the host (one download of the BVH2) */
-		std::vector<float> n2( (size_t)m.nodeCount * 16 );
-		CHK_HIP( hipMemcpyAsync( n2.data(), m.bvhNodes.ptr, n2.size() * sizeof( float ), hipMemcpyDeviceToHost, stream ) );
-		CHK_HIP( hipStreamSynchronize( stream ) );
-		BuildBlas4( m, n2.data() );
-	}
-	CHK_HIP( hipStreamSynchronize( stream ) );   /* the caller's triangle array is borrowed for this call only */
-	geometryDirty = true;
-	coreStats.bvhBuildTime += std::chrono::duration<float>( std::chrono::high_resolution_clock::now() - t0 ).count();
+	accel.SetGeometry( meshIdx, triangleCount, tris );
 }
-
-/* the deferred CPU BLAS builds (SetGeometry), in parallel over the meshes on up to `buildThreads` host threads
-   (a mesh's own build gets the threads left over when there are fewer meshes than threads), then their upload */
-void RenderCore::FlushBuilds()
-{
-	if (!pendingBuilds) return;
-	pendingBuilds = false;
-	const auto t0 = std::chrono::high_resolution_clock::now();
-	std::vector<CoreMeshHost*> jobs;
-	for (auto* m : meshes) if (m->build) jobs.push_back( m );
-	int workers = buildThreads;
-	if (workers <= 0)
-	{
-		const char* e = getenv( "LH2_BUILD_THREADS" );
-		if (!e) e = getenv( "OMP_NUM_THREADS" );
-		const unsigned hw = std::thread::hardware_concurrency();
-		workers = e && atoi( e ) > 0 ? atoi( e ) : (int)std::min( 16u, hw ? hw : 4u );
-	}
-	const int nthreads = std::max( 1, std::min( workers, (int)jobs.size() ) );
-	const int perJob = std::max( 1, workers / std::max( 1, (int)jobs.size() ) );
-	std::atomic<int> next{ 0 }, inUse{ 0 };
-	std::vector<std::string> errors( nthreads );
-	/* the last jobs, fewer than the workers, get the idle workers' share as threads of their own build (SBVH subtrees):
-	   a job is granted threads only out of those no running build holds, so the total stays near `workers` */
-	auto work = [&]( int w ) {
-		try
-		{
-			for (int j; (j = next.fetch_add( 1 )) < (int)jobs.size();)
-			{
-				const int remaining = (int)jobs.size() - j;
-				const int want = std::max( perJob, std::min( 8, workers / std::max( 1, remaining ) ) );
-				/* reserve the grant atomically out of the threads no running build holds (one at least: this worker's own) */
-				int held = inUse.load(), grant = 1;
-				do grant = std::max( 1, std::min( want, workers - held ) );
-				while (!inUse.compare_exchange_weak( held, held + grant ));
-				jobs[j]->build->Run( grant );
-				inUse -= grant;
-			}
-		}
-		catch (const std::exception& e) { errors[w] = e.what(); }
-	};
-	std::vector<std::thread> pool;
-	for (int w = 1; w < nthreads; w++) pool.emplace_back( work, w );
-	work( 0 );
-	for (auto& t : pool) t.join();
-	for (auto& e : errors) if (!e.empty()) FatalError( "BLAS build: %s", e.c_str() );
-	for (auto* m : jobs)
-	{
-		const HostBlas& r = *m->build;
-		m->leafTris = r.leafTris, m->nodeCount = r.nodeCount, m->maxDepth = r.maxDepth, m->depth4 = r.depth4;
-		m->bvhNodes.upload( (const float4*)r.nodes2.data(), r.nodes2.size() / 4, stream );
-		m->bvhTris.upload( (const float4*)r.tris48.data(), r.tris48.size() / 4, stream );
-		if (bvh4) m->bvh4Nodes.upload( (const float4*)r.nodes4.data(), r.nodes4.size() / 4, stream ), m->node4Count = (int)(r.nodes4.size() / 32);
-		CHK_HIP( hipStreamSynchronize( stream ) );
-		m->build.reset();   /* the last core to upload a shared build frees its host arrays */
-	}
-	coreStats.bvhBuildTime += std::chrono::duration<float>( std::chrono::high_resolution_clock::now() - t0 ).count();
-}
-
-/* MultiDevice's sub-cores: the mesh of src (core 0, which has just taken it through SetGeometry), its shading triangles
-   uploaded to this device, its deferred CPU build shared (run once by the first core to flush, uploaded by each).  A GPU
-   build (gpuBuild), or a mesh src has already uploaded, is built here as SetGeometry builds it */
 void RenderCore::AdoptGeometry( int meshIdx, int triangleCount, const lh2_CoreTri* tris, const RenderCore& src )
 {
-	const CoreMeshHost* sm = meshIdx >= 0 && meshIdx < (int)src.meshes.size() ? src.meshes[meshIdx] : nullptr;
-	if (!sm || !sm->build || sm->triCount != triangleCount || bvh4 != src.bvh4)
-	{
-		SetGeometry( meshIdx, nullptr, 0, triangleCount, tris, nullptr );
-		return;
-	}
 	sceneVersion++;
-	if (meshIdx < 0 || meshIdx > (int)meshes.size()) FatalError( "SetGeometry: mesh index %d out of sequence", meshIdx );
-	if (meshIdx == (int)meshes.size()) meshes.push_back( new CoreMeshHost() );
-	CoreMeshHost& m = *meshes[meshIdx];
-	const auto t0 = std::chrono::high_resolution_clock::now();
-	m.triCount = triangleCount;
-	m.shadeTris.upload( (const float4*)tris, (size_t)triangleCount * 11, stream );
-	m.shadeTris.resize( 11 );
-	for (int k = 0; k < 3; k++) m.aabbLo[k] = sm->aabbLo[k], m.aabbHi[k] = sm->aabbHi[k];
-	m.build = sm->build;
-	pendingBuilds = true;
-	CHK_HIP( hipStreamSynchronize( stream ) );   /* the caller's triangle array is borrowed for this call only */
-	geometryDirty = true;
-	coreStats.bvhBuildTime += std::chrono::duration<float>( std::chrono::high_resolution_clock::now() - t0 ).count();
+	accel.AdoptGeometry( meshIdx, triangleCount, tris, src.accel );
 }
+void RenderCore::UpdateToplevel() { if (accel.UpdateToplevel()) sceneVersion++; }
 
 #ifdef LH2_TOUCH
 /* the unique records one closest-hit launch reads (diagnostic build): quantized BVH4 nodes (64 B) and leaf triangle records
@@ -673,7 +462,7 @@ void RenderCore::AdoptGeometry( int meshIdx, int triangleCount, const lh2_CoreTr
 void RenderCore::TouchBegin()
 {
 	CHK_HIP( hipDeviceSynchronize() );   /* nothing in flight reads the bitmap pointer while it changes */
-	const uint32_t nodeWords = (uint32_t)(((size_t)blasNode4Count + 2 * tlasCapacity + 31) / 32), triWords = (uint32_t)(((size_t)blasTriCount + 31) / 32);
+	const uint32_t nodeWords = accel.TouchNodeWords(), triWords = accel.TouchTriWords();
 	touchMap.resize( (size_t)nodeWords + triWords );
 	CHK_HIP( hipMemsetAsync( touchMap.ptr, 0, sizeof( uint32_t ) * ((size_t)nodeWords + triWords), stream ) );
 	lh2_touch_set( touchMap.ptr, nodeWords, nodeWords + triWords );
@@ -688,255 +477,10 @@ void RenderCore::TouchReport( int pathLength )
 	for (size_t i = 0; i < h.size(); i++) (i < touchNodeWords ? nodes : tris) += (uint64_t)__builtin_popcount( h[i] );
 	fprintf( stderr, "LH2_TOUCH {\"pathLength\": %d, \"unique_nodes\": %llu, \"unique_tri_records\": %llu, \"node_bytes\": %llu, "
 		"\"tri_bytes\": %llu, \"scene_nodes\": %d, \"scene_tri_records\": %d, \"paths\": %u}\n", pathLength, (unsigned long long)nodes,
-		(unsigned long long)tris, (unsigned long long)nodes * 64ull, (unsigned long long)tris * 48ull, blasNode4Count, blasTriCount, ps.count );
+		(unsigned long long)tris, (unsigned long long)nodes * 64ull, (unsigned long long)tris * 48ull, accel.Node4Count(), accel.TriRecordCount(), ps.count );
 	lh2_touch_set( nullptr, 0, 0 );   /* later closest-hit launches (unit queries) record nothing */
 }
 #endif
-
-void RenderCore::BuildBlas4( CoreMeshHost& m, const float* nodes2 )
-{
-	std::vector<float> n4;
-	/* bvh4Collapse 1: dynamic-programming collapse (surface-area costs, optional leaf merging); 0: greedy */
-	/* node step = 1, leaf visit 0.4, triangle test 0.5; one triangle per leaf (merged leaves run the leaf loop
-	   divergent: slower, profiles/r02s_ab_collapse_shade4.txt) */
-	m.depth4 = bvh4Collapse ? CollapseBvh4Sah( nodes2, (size_t)m.nodeCount, n4, 0.4f, 0.5f, 1 )
-		: CollapseBvh4( nodes2, (size_t)m.nodeCount, n4 );
-	m.bvh4Nodes.upload( (const float4*)n4.data(), n4.size() / 4, stream );
-	m.node4Count = (int)(n4.size() / 32);
-}
-
-void RenderCore::SetInstance( int instanceIdx, int meshIdx, const float* M )   /* rendercore.cpp:229-243 */
-{
-	/* host state only: UpdateToplevel writes it into the TLAS slot no frame in flight reads */
-	if (meshIdx == -1) { if ((int)instances.size() > instanceIdx) instances.resize( instanceIdx ); instancesDirty = true; return; }
-	if (meshIdx < 0 || meshIdx >= (int)meshes.size()) FatalError( "SetInstance: unknown mesh %d", meshIdx );
-	if (instanceIdx >= (int)instances.size()) instances.resize( instanceIdx + 1 );
-	instances[instanceIdx].mesh = meshIdx;
-	memcpy( instances[instanceIdx].T, M, 64 );
-	instancesDirty = true;
-}
-
-/* scene node array = all BLAS (relocated, device to device) followed by room for the TLAS */
-void RenderCore::ConcatenateBlas( int ni )
-{
-	FlushBuilds();
-	meshNodeBase.assign( meshes.size(), 0 ), meshTriBase.assign( meshes.size(), 0 ), meshNode4Base.assign( meshes.size(), 0 );
-	int nodeTotal = 0, triTotal = 0, node4Total = 0, meshTris = 0;
-	maxBlasDepth = 0, maxBlas4Depth = 0;
-	std::vector<float> bounds( std::max<size_t>( meshes.size(), 1 ) * 6, 0.0f );
-	for (size_t mi = 0; mi < meshes.size(); mi++)
-	{
-		const CoreMeshHost& m = *meshes[mi];
-		meshNodeBase[mi] = nodeTotal, meshTriBase[mi] = triTotal, meshNode4Base[mi] = node4Total;
-		nodeTotal += m.nodeCount, triTotal += m.leafTris, node4Total += m.node4Count, meshTris += m.triCount;
-		maxBlasDepth = std::max( maxBlasDepth, m.maxDepth ), maxBlas4Depth = std::max( maxBlas4Depth, m.depth4 );
-		for (int k = 0; k < 3; k++) bounds[mi * 6 + k] = m.aabbLo[k], bounds[mi * 6 + 3 + k] = m.aabbHi[k];
-		if (m.triCount == 0) bounds[mi * 6] = 1.0f, bounds[mi * 6 + 3] = 0.0f;   /* empty-mesh marker */
-	}
-	tlasCapacity = std::max( 64, 2 * ni + 16 );
-	/* frames in flight may still read the old arrays, and a TLAS update may be queued on the ahead stream */
-	CHK_HIP( hipStreamSynchronize( stream ) );
-	CHK_HIP( hipStreamSynchronize( aheadStream ) );
-	dNodes.free(), dTris.free(), dNodes4.free(), dNodes4q.free();
-	/* after the BLAS: two TLAS slots of tlasCapacity nodes each (UpdateToplevel) */
-	dNodes.resize( ((size_t)nodeTotal + 2 * tlasCapacity) * 4 );
-	/* the BVH4 loops address nodes with 32-bit buffer offsets (lh2_trace4d.inc): the array stays below 2 GiB */
-	if (bvh4 && ((size_t)node4Total + 2 * tlasCapacity) * 128 > 0x7fffffffull)
-		FatalError( "BVH4 of %zu nodes exceeds the 2 GiB the traversal addresses", (size_t)node4Total + 2 * tlasCapacity );
-	if (bvh4) dNodes4.resize( ((size_t)node4Total + 2 * tlasCapacity) * 8 ), dNodes4q.resize( ((size_t)node4Total + 2 * tlasCapacity) * 4 );
-	dTris.resize( (size_t)std::max( triTotal, 1 ) * 3 );
-	/* the TLAS region starts as NaN boxes: a TLAS of fewer nodes than the capacity leaves no uninitialised (possibly huge,
-	   finite) boxes behind it for the quantizer's range check (k_quantize4) */
-	CHK_HIP( hipMemsetAsync( dNodes.ptr + (size_t)nodeTotal * 4, 0xff, sizeof( float4 ) * 4 * 2 * (size_t)tlasCapacity, stream ) );
-	dBlasQError.resize( 1 );
-	CHK_HIP( hipMemsetAsync( dBlasQError.ptr, 0, sizeof( int ), stream ) );
-	for (size_t mi = 0; mi < meshes.size(); mi++)
-	{
-		const CoreMeshHost& m = *meshes[mi];
-		GpuBvhBuilder::Relocate( m.bvhNodes.ptr, m.nodeCount, meshNodeBase[mi], (uint32_t)meshTriBase[mi], dNodes.ptr, stream );
-		if (bvh4) GpuBvhBuilder::Relocate4( m.bvh4Nodes.ptr, m.node4Count, meshNode4Base[mi], (uint32_t)meshTriBase[mi], dNodes4.ptr, stream );
-		if (m.leafTris) CHK_HIP( hipMemcpyAsync( dTris.ptr + (size_t)meshTriBase[mi] * 3, m.bvhTris.ptr, sizeof( float4 ) * 3 * (size_t)m.leafTris, hipMemcpyDeviceToDevice, stream ) );
-	}
-	if (bvh4) GpuBvhBuilder::Quantize4( dNodes4.ptr, 0, node4Total, dNodes4q.ptr, dBlasQError.ptr, stream );
-	dMeshBounds.upload( bounds.data(), bounds.size(), stream );
-	CHK_HIP( hipStreamSynchronize( stream ) );
-	blasNodeCount = nodeTotal, blasTriCount = triTotal, blasNode4Count = node4Total, blasMeshTris = meshTris;
-	geometryDirty = false;
-}
-
-void RenderCore::UpdateToplevel()   /* rendercore.cpp:250-270 (TLAS) + :481-505 (instance descriptors) */
-{
-	const int ni = (int)instances.size();
-	if (geometryDirty || ni + 1 > tlasCapacity)
-	{
-		sceneVersion++;   /* new BLAS arrays: the next fused frame's primary launch waits for the previous frame */
-		ConcatenateBlas( ni );
-	}
-	/* the TLAS slot no frame in flight reads (the other one is the last frame's), written on the ahead stream behind the
-	   last frame that read it; instance-only updates leave sceneVersion alone, so the next frame may still overlap */
-	const int ts = tlasSlot ^ 1;
-	hipStream_t us = aheadStream;
-	if (tlasFreeValid[ts]) CHK_HIP( hipStreamWaitEvent( us, evTlasFree[ts], 0 ) );
-	tlasRoot = TlasBase2( ts );
-	/* host part: inverse transforms and instance records, written to pinned staging (double-buffered)
-	   and copied asynchronously; no host-device round trip per frame */
-	const int slot = stageSlot;
-	stageSlot ^= 1;
-	const size_t nRec = (size_t)std::max( ni, 1 );
-	const size_t offInst = 0, offDesc = offInst + nRec * sizeof( DevInstance ), offT = offDesc + nRec * sizeof( lh2_CoreInstanceDesc );
-	const size_t offMesh = offT + nRec * 64, offNodes = offMesh + nRec * 4, need = offNodes + 4 * 64 * nRec + 64;
-	CHK_HIP( hipEventSynchronize( evStage[slot] ) );   /* the copies from this slot two updates ago are done */
-	if (need > stageBytes[slot])
-	{
-		if (stage[slot]) CHK_HIP( hipHostFree( stage[slot] ) );
-		stageBytes[slot] = need + need / 2;
-		CHK_HIP( hipHostMalloc( (void**)&stage[slot], stageBytes[slot], hipHostMallocDefault ) );
-	}
-	uint8_t* sb = stage[slot];
-	DevInstance* di = (DevInstance*)(sb + offInst);
-	lh2_CoreInstanceDesc* desc = (lh2_CoreInstanceDesc*)(sb + offDesc);
-	float* Ts = (float*)(sb + offT);
-	int* meshIds = (int*)(sb + offMesh);
-	memset( sb, 0, offMesh + nRec * 4 );
-	for (int i = 0; i < ni; i++)
-	{
-		CoreInstanceHost& in = instances[i];
-		Mat4Inverse( in.T, in.inv );
-		di[i].inv0 = make_float4( in.inv[0], in.inv[1], in.inv[2], in.inv[3] );
-		di[i].inv1 = make_float4( in.inv[4], in.inv[5], in.inv[6], in.inv[7] );
-		di[i].inv2 = make_float4( in.inv[8], in.inv[9], in.inv[10], in.inv[11] );
-		di[i].root = meshNodeBase[in.mesh], di[i].triBase = meshTriBase[in.mesh], di[i].mesh = in.mesh;
-		di[i].root4 = bvh4 ? meshNode4Base[in.mesh] : 0;
-		desc[i].triangles = meshes[in.mesh]->shadeTris.ptr;
-		desc[i].A = { in.inv[0], in.inv[1], in.inv[2], in.inv[3] };
-		desc[i].B = { in.inv[4], in.inv[5], in.inv[6], in.inv[7] };
-		desc[i].C = { in.inv[8], in.inv[9], in.inv[10], in.inv[11] };
-		desc[i].D = { in.inv[12], in.inv[13], in.inv[14], in.inv[15] };
-		memcpy( Ts + (size_t)i * 16, in.T, 64 );
-		meshIds[i] = in.mesh;
-	}
-	/* the scene's world box (instance transforms of the mesh boxes): the shade launches order extension
-	   rays by their chord through it (ShadeParams::chordCut) */
-	for (int k = 0; k < 3; k++) sceneLo[k] = 1e30f, sceneHi[k] = -1e30f;
-	for (int i = 0; i < ni; i++)
-	{
-		const CoreInstanceHost& in = instances[i];
-		const CoreMeshHost& m = *meshes[in.mesh];
-		if (m.triCount == 0) continue;
-		for (int c = 0; c < 8; c++)
-		{
-			const float x = c & 1 ? m.aabbHi[0] : m.aabbLo[0], y = c & 2 ? m.aabbHi[1] : m.aabbLo[1], z = c & 4 ? m.aabbHi[2] : m.aabbLo[2];
-			for (int k = 0; k < 3; k++)
-			{
-				const float w = in.T[k * 4 + 0] * x + in.T[k * 4 + 1] * y + in.T[k * 4 + 2] * z + in.T[k * 4 + 3];
-				sceneLo[k] = std::min( sceneLo[k], w ), sceneHi[k] = std::max( sceneHi[k], w );
-			}
-		}
-	}
-	/* the quantized nodes' origins lie in these boxes (TLAS: world; BLAS: mesh space); 1 % slack for the
-	   device-side TLAS bounds' own rounding */
-	qBound = 0;
-	for (int k = 0; k < 3; k++) qBound = std::max( qBound, std::max( fabsf( sceneLo[k] ), fabsf( sceneHi[k] ) ) );
-	for (const auto& m : meshes)
-		if (m->triCount) for (int k = 0; k < 3; k++) qBound = std::max( qBound, std::max( fabsf( m->aabbLo[k] ), fabsf( m->aabbHi[k] ) ) );
-	qBound = qBound * 1.01f + 1e-30f;
-	/* a slot's tables grow only with the work that may read them drained (DevBuf::resize frees the old buffer) */
-	if (dInst[ts].count < nRec * sizeof( DevInstance ) || dInstDesc[ts].count < nRec || dInstT.count < nRec * 16 || dInstMesh.count < nRec)
-	{
-		CHK_HIP( hipStreamSynchronize( stream ) );
-		CHK_HIP( hipStreamSynchronize( us ) );
-		dInst[ts].resize( nRec * sizeof( DevInstance ) ), dInstDesc[ts].resize( nRec ), dInstT.resize( nRec * 16 ), dInstMesh.resize( nRec );
-	}
-	CHK_HIP( hipMemcpyAsync( dInst[ts].ptr, di, nRec * sizeof( DevInstance ), hipMemcpyHostToDevice, us ) );
-	CHK_HIP( hipMemcpyAsync( dInstDesc[ts].ptr, desc, nRec * sizeof( lh2_CoreInstanceDesc ), hipMemcpyHostToDevice, us ) );
-	/* the scene error starts as the BLAS quantizer's (ConcatenateBlas), the TLAS checks add to it */
-	CHK_HIP( hipMemcpyAsync( SceneErr( ts ), dBlasQError.ptr, sizeof( int ), hipMemcpyDeviceToDevice, us ) );
-	int tlasNodes = 1;   /* the nodes this TLAS has (the slot holds tlasCapacity): the BVH4 copy and the quantizer touch no others */
-	if (ni >= 2 && gpuTlas)
-	{
-		/* TLAS built on the device from the instance transforms (bvh_gpu.h) */
-		CHK_HIP( hipMemcpyAsync( dInstT.ptr, Ts, nRec * 64, hipMemcpyHostToDevice, us ) );
-		CHK_HIP( hipMemcpyAsync( dInstMesh.ptr, meshIds, nRec * 4, hipMemcpyHostToDevice, us ) );
-		GpuTlasArgs ta;
-		ta.T = dInstT.ptr, ta.instMesh = dInstMesh.ptr, ta.meshBounds = dMeshBounds.ptr, ta.count = ni;
-		ta.nodeBase = TlasBase2( ts ), ta.nodes = dNodes.ptr, ta.maxBlasDepth = StackDepthBound();
-		ta.sceneError = SceneErr( ts ), ta.tlasDepth = dTlasDepth.ptr;
-		ta.tlasFactor = 1;
-		gpuBvh.BuildTlas( ta, us );
-		tlasNodes = ni - 1;   /* one instance per leaf: ni - 1 child-pair nodes, dense in preorder (bvh_gpu.hip emit_node) */
-		tlasOnDevice = true;
-		sceneMaxDepth = -1;   /* known on the device; SceneInfo reads it */
-	}
-	else
-	{
-		/* host TLAS (binned SAH) over instance world bounds, 1 instance per leaf */
-		std::vector<Aabb> prims;
-		std::vector<int> primInst;
-		for (int i = 0; i < ni; i++)
-		{
-			const CoreInstanceHost& in = instances[i];
-			const CoreMeshHost& m = *meshes[in.mesh];
-			if (m.triCount == 0) continue;
-			Aabb b;
-			for (int k = 0; k < 3; k++) b.lo[k] = 1e30f, b.hi[k] = -1e30f;
-			for (int c = 0; c < 8; c++)
-			{
-				const float p[3] = { (c & 1) ? m.aabbHi[0] : m.aabbLo[0], (c & 2) ? m.aabbHi[1] : m.aabbLo[1], (c & 4) ? m.aabbHi[2] : m.aabbLo[2] };
-				for (int k = 0; k < 3; k++)
-				{
-					const float* r = in.T + k * 4;
-					const float v = r[0] * p[0] + r[1] * p[1] + r[2] * p[2] + r[3];
-					b.lo[k] = std::min( b.lo[k], v ), b.hi[k] = std::max( b.hi[k], v );
-				}
-			}
-			/* pad by a relative epsilon: the ray is transformed in fp32 on the device */
-			for (int k = 0; k < 3; k++)
-			{
-				const float e = 1e-5f * std::max( std::fabs( b.lo[k] ), std::fabs( b.hi[k] ) ) + 1e-30f;
-				b.lo[k] -= e, b.hi[k] += e;
-			}
-			prims.push_back( b ), primInst.push_back( i );
-		}
-		BvhOutput tlas;
-		BuildBvh2( prims, 1, 1, tlas );
-		const size_t tn = tlas.nodes.size() / 16;
-		if (tn > (size_t)tlasCapacity) FatalError( "TLAS of %zu nodes exceeds its capacity %d", tn, tlasCapacity );
-		tlasNodes = std::max( 1, (int)tn );
-		for (size_t k = 0; k < tn; k++)
-		{
-			int* refs = (int*)&tlas.nodes[k * 16 + 12];
-			for (int c = 0; c < 2; c++)
-			{
-				if (refs[c] >= 0) refs[c] += TlasBase2( ts );
-				else if (!prims.empty())
-				{
-					if (LEAF_COUNT( refs[c] ) != 1) FatalError( "TLAS leaf with %d instances", LEAF_COUNT( refs[c] ) );
-					refs[c] = MAKE_LEAF( (uint32_t)primInst[tlas.perm[LEAF_FIRST( refs[c] )]], 1 );
-				}
-			}
-		}
-		if (tlas.nodes.size() * sizeof( float ) > need - offNodes) FatalError( "TLAS staging overflow" );
-		memcpy( sb + offNodes, tlas.nodes.data(), tlas.nodes.size() * sizeof( float ) );
-		CHK_HIP( hipMemcpyAsync( dNodes.ptr + (size_t)TlasBase2( ts ) * 4, sb + offNodes, tlas.nodes.size() * sizeof( float ), hipMemcpyHostToDevice, us ) );
-		sceneMaxDepth = tlas.maxDepth + StackDepthBound();
-		tlasOnDevice = false;
-		if (sceneMaxDepth >= LH2_STACK_TOTAL - 1) FatalError( "BVH depth %d exceeds the traversal stack (%d)", sceneMaxDepth, LH2_STACK_TOTAL );
-	}
-	/* the TLAS in the BVH4 array: its BVH2 nodes as two-child BVH4 nodes (one short launch), quantized.  Only the nodes this
-	   TLAS has: the slot's nodes beyond them hold an earlier, larger TLAS or memory never written, whose boxes (possibly huge,
-	   finite) would set the quantizer's range error (round 4 fixed that by NaN-filling the region, 651cce0; no traversal ever
-	   reaches such a node, so it is not read at all now; test_gpu_parity.py::test_stale_tlas_region_is_not_quantized) */
-	if (bvh4)
-	{
-		GpuBvhBuilder::TlasToBvh4( dNodes.ptr, TlasBase2( ts ), tlasNodes, TlasBase4( ts ), dNodes4.ptr, us );
-		GpuBvhBuilder::Quantize4( dNodes4.ptr, TlasBase4( ts ), tlasNodes, dNodes4q.ptr, SceneErr( ts ), us );
-	}
-	tlasNodeCount[ts] = tlasNodes;
-	CHK_HIP( hipEventRecord( evStage[slot], us ) );
-	CHK_HIP( hipEventRecord( evTlasReady, us ) );
-	tlasSlot = ts, tlasPending = true;
-	instancesDirty = false;
-}
 
 /* device-side scene errors (TLAS deeper than the traversal stack): the trace kernels skip the
    frame, and the host reports it here */
@@ -950,45 +494,23 @@ static const char* SceneErrorText( int e )
 
 void RenderCore::CheckSceneError()
 {
-	if (!dSceneError.ptr) return;
+	const int* err = accel.SceneErr( accel.Slot() );
+	if (!err) return;
 	int e = 0;
-	SyncTlas();
-	CHK_HIP( hipMemcpyAsync( &hostStats->sceneError, SceneErr( tlasSlot ), sizeof( int ), hipMemcpyDeviceToHost, stream ) );
+	accel.SyncTlas();
+	CHK_HIP( hipMemcpyAsync( &hostStats->sceneError, err, sizeof( int ), hipMemcpyDeviceToHost, stream ) );
 	CHK_HIP( hipStreamSynchronize( stream ) );
 	e = hostStats->sceneError;
 	if (e) FatalError( "%s", SceneErrorText( e ) );
 }
 
-/* the core stream's next launch reads the TLAS slot the last UpdateToplevel wrote on the ahead stream */
-void RenderCore::SyncTlas()
-{
-	if (!tlasPending) return;
-	CHK_HIP( hipStreamWaitEvent( stream, evTlasReady, 0 ) );
-	tlasPending = false;
-}
-
 SceneDev RenderCore::MakeSceneDev()
 {
-	SyncTlas();
 	SceneDev s;
-	s.nodes = dNodes.ptr, s.tris = dTris.ptr, s.inst = (const DevInstance*)dInst[tlasSlot].ptr;
-	s.sceneError = SceneErr( tlasSlot );
+	accel.Fill( s, singleInstanceStart );
 	s.argb32 = dArgb32.ptr, s.nrm32 = dNrm32.ptr;
 	s.argb32Count = (uint32_t)dArgb32.count, s.nrm32Count = (uint32_t)dNrm32.count;
-	s.tlasRoot = tlasRoot, s.instCount = (int)instances.size();
-	s.nodes4 = dNodes4.ptr, s.nodes4q = dNodes4q.ptr, s.qBound = qBound, s.tlasRoot4 = TlasBase4( tlasSlot );
-	/* one instance of a non-empty mesh: rays start at its TLAS leaf (MAKE_LEAF( 0, 1 ) = ~0) and skip
-	   the TLAS root's box test, which can only cull (TopLevelBVH::Traverse bvh.cpp:594-649); the
-	   instance transform runs as at the leaf, so the hits are unchanged: one loop iteration less per ray */
-	s.root40 = 0, s.tris0 = nullptr;
-	if (singleInstanceStart && instances.size() == 1 && instances[0].mesh >= 0 && instances[0].mesh < (int)meshes.size() &&
-		meshes[instances[0].mesh]->triCount > 0)
-	{
-		s.tlasRoot = s.tlasRoot4 = ~0;
-		s.root40 = bvh4 ? meshNode4Base[instances[0].mesh] : 0;   /* DevInstance::root4 of instance 0 (UpdateToplevel) */
-		s.tris0 = meshes[instances[0].mesh]->shadeTris.ptr;       /* lh2_CoreInstanceDesc::triangles of instance 0 */
-	}
-	s.instDesc = dInstDesc[tlasSlot].ptr, s.materials = dMaterials.ptr;
+	s.materials = dMaterials.ptr;
 	s.areaLights = dArea.ptr, s.pointLights = dPoint.ptr, s.spotLights = dSpot.ptr, s.dirLights = dDir.ptr;
 	s.nArea = nArea, s.nPoint = nPoint, s.nSpot = nSpot, s.nDir = nDir;
 	s.sky = dSky.ptr, s.skyW = skyW, s.skyH = skyH;
@@ -1013,7 +535,7 @@ struct Frame
 	const FramePlan plan;
 	const lh2_ViewPyramid& view;
 	SceneDev sd{};
-	int tlas = 0;                        /* the TLAS slot this frame reads (evTlasFree after its finalize) */
+	int tlas = 0;                        /* the TLAS slot this frame reads (released after its finalize) */
 	FrameSlots s{};                      /* this frame's parity: its counters, work-queue heads, shadow stream and ray-count log */
 	CameraParams cp{};
 	int in = 0;                          /* the ping-pong set the bounce reads; its shade launch writes the other one */
@@ -1037,7 +559,7 @@ void RenderCore::Render( const lh2_ViewPyramid& view, int converge )   /* render
 {
 	if (!initialized) FatalError( "Render before Init" );
 	if (!scrwidth) FatalError( "Render before SetTarget" );
-	if (geometryDirty || instancesDirty) UpdateToplevel();
+	if (accel.Dirty()) UpdateToplevel();
 	if (!dMaterials.ptr) FatalError( "Render before SetMaterials" );
 	const auto t0 = std::chrono::high_resolution_clock::now();
 	Frame f{ PlanFrame( view, converge ), view };
@@ -1173,7 +695,7 @@ void RenderCore::BeginFrame( Frame& f, int converge )
 	   reference, but keeps the history) */
 	if (p.filt && converge == LH2_RESTART) fl.historyValid = false;
 	f.sd = MakeSceneDev();
-	f.tlas = tlasSlot;
+	f.tlas = accel.Slot();
 	if (p.clearAll) CHK_HIP( hipMemsetAsync( accumulator.ptr, 0, sizeof( float4 ) * (size_t)scrwidth * scrheight, stream ) );
 	EnsurePaths( p.pathCount );
 	/* shadow rays in segments of shadowStride */
@@ -1362,6 +884,7 @@ void RenderCore::ShadeBounce( Frame& f, int pathLength )
 	sp.segBack = c->segBack[(pathLength - 1) & 1], sp.segOutBack = c->segBack[pathLength & 1];
 	/* two-ended path segments: rays with a chord through the scene box below chordSplit x its largest
 	   extent go last (setting "chordSplit"; 0: off) */
+	const float *sceneLo = accel.WorldLo(), *sceneHi = accel.WorldHi();
 	const float ext = std::max( std::max( sceneHi[0] - sceneLo[0], sceneHi[1] - sceneLo[1] ), sceneHi[2] - sceneLo[2] );
 	for (int k = 0; k < 3; k++) sp.chordLo[k] = sceneLo[k], sp.chordHi[k] = sceneHi[k];
 	sp.chordCut = ext > 0 ? chordSplit * ext : 0.0f;
@@ -1487,7 +1010,7 @@ void RenderCore::FinishFrame( Frame& f )
 	if (f.sideOn) CHK_HIP( hipStreamWaitEvent( stream, ps.evSide, 0 ) );
 	samplesTaken += scrspp;
 	/* finalize also delivers the frame's counters and ray-count log, and the scene error, to hostStats */
-	const FrameStatsDev fs{ f.s.c, f.s.rayLog + 1, &hostStats->counters, hostStats->rayCount + 1, SceneErr( f.tlas ), &hostStats->sceneError,
+	const FrameStatsDev fs{ f.s.c, f.s.rayLog + 1, &hostStats->counters, hostStats->rayCount + 1, accel.SceneErr( f.tlas ), &hostStats->sceneError,
 		f.s.Cursor( kPrimarySlot ), p.early ? f.s.delta : nullptr };
 	/* a tile finalizes its own rows only (a rank of the band partition: the gathered frame is finalized
 	   where it is assembled, MultiDevice / FinalizeFrame) */
@@ -1507,8 +1030,7 @@ void RenderCore::FinishFrame( Frame& f )
 	}
 	else lh2_launch_finalize( accumulator.ptr, frame.ptr, scrwidth * scrheight, 1.0f / (float)samplesTaken, &fs, { nullptr, evFrame[1] }, stream, &rm );
 	frameEndRecorded = true;
-	CHK_HIP( hipEventRecord( evTlasFree[f.tlas], stream ) );   /* the next update of this TLAS slot waits for it */
-	tlasFreeValid[f.tlas] = true;
+	accel.ReleaseSlot( f.tlas, stream );   /* the next update of this TLAS slot waits for it */
 	if (glResource && !displayAtFinalize) CopyFrameToDisplay();
 	hostStats->rayCount[0] = ps.count;
 	ps.lastFused = p.pFrame, ps.lastSceneVersion = sceneVersion;
@@ -1770,6 +1292,7 @@ void RenderCore::Synchronize()
 lh2_CoreStats RenderCore::GetCoreStats()
 {
 	Synchronize();
+	coreStats.bvhBuildTime = accel.BuildSeconds();
 	return coreStats;
 }
 
@@ -1801,41 +1324,16 @@ int RenderCore::DebugShadowRays( float* o4, float* d4, float* p4, int cap )
 
 int RenderCore::DebugBvh4( float* f32Nodes, uint32_t* qNodes, int cap )
 {
-	if (geometryDirty || instancesDirty) UpdateToplevel();
+	if (accel.Dirty()) UpdateToplevel();
 	Synchronize();
-	SyncTlas();
-	CHK_HIP( hipStreamSynchronize( stream ) );
-	if (!dNodes4.ptr || !dNodes4q.ptr) return 0;
-	const int tn = tlasNodeCount[tlasSlot];   /* the current TLAS's own nodes (the slot's others are never written, §3) */
-	if (cap <= 0 || !f32Nodes || !qNodes) return blasNode4Count + tn;   /* a count-only call */
-	/* the BLAS nodes, then the current TLAS slot's */
-	const int n = std::min( cap, blasNode4Count + tn ), nb = std::min( n, blasNode4Count ), nt = n - nb;
-	CHK_HIP( hipMemcpy( f32Nodes, dNodes4.ptr, 128 * (size_t)nb, hipMemcpyDeviceToHost ) );
-	CHK_HIP( hipMemcpy( qNodes, dNodes4q.ptr, 64 * (size_t)nb, hipMemcpyDeviceToHost ) );
-	if (nt > 0)
-	{
-		CHK_HIP( hipMemcpy( f32Nodes + 32 * (size_t)nb, dNodes4.ptr + 8 * (size_t)TlasBase4( tlasSlot ), 128 * (size_t)nt, hipMemcpyDeviceToHost ) );
-		CHK_HIP( hipMemcpy( qNodes + 16 * (size_t)nb, dNodes4q.ptr + 4 * (size_t)TlasBase4( tlasSlot ), 64 * (size_t)nt, hipMemcpyDeviceToHost ) );
-	}
-	return n;
+	return accel.DebugBvh4( f32Nodes, qNodes, cap );
 }
 
-/* diagnostics (test hook): fill both TLAS slots' node regions (BVH2 and BVH4, f32 and quantized) with `value`, as memory an
-   earlier, larger TLAS or an uninitialised allocation leaves behind the nodes a TLAS update writes */
 void RenderCore::DebugPoisonTlas( float value )
 {
-	if (geometryDirty || instancesDirty) UpdateToplevel();
+	if (accel.Dirty()) UpdateToplevel();
 	Synchronize();
-	SyncTlas();
-	CHK_HIP( hipStreamSynchronize( stream ) );
-	CHK_HIP( hipStreamSynchronize( aheadStream ) );
-	std::vector<float> fill( (size_t)2 * tlasCapacity * 32, value );
-	CHK_HIP( hipMemcpy( dNodes.ptr + (size_t)blasNodeCount * 4, fill.data(), sizeof( float4 ) * 4 * 2 * (size_t)tlasCapacity, hipMemcpyHostToDevice ) );
-	if (bvh4)
-	{
-		CHK_HIP( hipMemcpy( dNodes4.ptr + (size_t)blasNode4Count * 8, fill.data(), sizeof( float4 ) * 8 * 2 * (size_t)tlasCapacity, hipMemcpyHostToDevice ) );
-		CHK_HIP( hipMemcpy( dNodes4q.ptr + (size_t)blasNode4Count * 4, fill.data(), sizeof( uint4 ) * 4 * 2 * (size_t)tlasCapacity, hipMemcpyHostToDevice ) );
-	}
+	accel.DebugPoisonTlas( value );
 }
 
 void RenderCore::GetAccumulator( float* hostOut4 )
@@ -1896,7 +1394,7 @@ TraceArgs RenderCore::UnitArgs( const float4* o, const float4* d, int n, uint32_
 
 void RenderCore::TraceClosest( const float* ot, const float* dt, int n, uint32_t* hits4 )
 {
-	if (geometryDirty || instancesDirty) UpdateToplevel();
+	if (accel.Dirty()) UpdateToplevel();
 	DevBuf<float4> o, d; DevBuf<uint4> h; DevBuf<int> gs; DevBuf<uint32_t> ovf;
 	o.upload( (const float4*)ot, n, stream ), d.upload( (const float4*)dt, n, stream );
 	h.resize( n ), ovf.resize( LH2_CURSOR_WORDS );
@@ -1912,7 +1410,7 @@ void RenderCore::TraceClosest( const float* ot, const float* dt, int n, uint32_t
 
 void RenderCore::TraceAny( const float* ot, const float* dt, int n, uint32_t* occluded )
 {
-	if (geometryDirty || instancesDirty) UpdateToplevel();
+	if (accel.Dirty()) UpdateToplevel();
 	DevBuf<float4> o, d; DevBuf<uint32_t> m; DevBuf<int> gs; DevBuf<uint32_t> ovf;
 	o.upload( (const float4*)ot, n, stream ), d.upload( (const float4*)dt, n, stream );
 	const size_t words = ((size_t)n + 63) / 64 * 2;
@@ -1933,7 +1431,7 @@ void RenderCore::TraceAny( const float* ot, const float* dt, int n, uint32_t* oc
 
 void RenderCore::TraceClosestDevice( const void* ro, const void* rd, int n, void* hitsOut, int iterations, float* msOut )
 {
-	if (geometryDirty || instancesDirty) UpdateToplevel();
+	if (accel.Dirty()) UpdateToplevel();
 	EnsureStack();
 	const SceneDev sd = MakeSceneDev();
 	DevBuf<uint32_t> cursors;
@@ -2011,19 +1509,8 @@ void RenderCore::GenerateEyeRays( const lh2_ViewPyramid& view, uint32_t R0, int 
 
 void RenderCore::SceneInfo( int* nodeCount, int* triCount, int* maxDepth, int* instCount )
 {
-	if (geometryDirty || instancesDirty) UpdateToplevel();
-	if (nodeCount) *nodeCount = blasNodeCount;
-	if (triCount) *triCount = blasMeshTris;
-	if (tlasOnDevice)
-	{
-		int d = 0;
-		SyncTlas();
-		CHK_HIP( hipMemcpyAsync( &d, dTlasDepth.ptr, sizeof( int ), hipMemcpyDeviceToHost, stream ) );
-		CHK_HIP( hipStreamSynchronize( stream ) );
-		sceneMaxDepth = d + maxBlasDepth;
-	}
-	if (maxDepth) *maxDepth = sceneMaxDepth;
-	if (instCount) *instCount = (int)instances.size();
+	if (accel.Dirty()) UpdateToplevel();
+	accel.SceneInfo( nodeCount, triCount, maxDepth, instCount );
 }
 
 #ifdef LH2_SHADE_TIMES
@@ -2043,9 +1530,7 @@ void RenderCore::Shutdown()   /* rendercore.cpp:615-650 */
 	}
 #endif
 	if (aheadStream) (void)hipStreamSynchronize( aheadStream );   /* a TLAS update nothing waited for */
-	for (auto* m : meshes) delete m;
-	meshes.clear();
-	instances.clear();
+	accel.Shutdown();
 	for (auto& e : ps.evTrace) (void)hipEventDestroy( e ), e = nullptr;
 	for (auto& e : ps.evShade) (void)hipEventDestroy( e ), e = nullptr;
 	for (auto& e : ps.evShadowB) (void)hipEventDestroy( e ), e = nullptr;
@@ -2056,9 +1541,6 @@ void RenderCore::Shutdown()   /* rendercore.cpp:615-650 */
 	for (hipEvent_t* e : { &evConsumer, &evPacked }) { if (*e) (void)hipEventDestroy( *e ); *e = nullptr; }
 	for (auto& e : fl.ev) { if (e) (void)hipEventDestroy( e ); e = nullptr; }
 	for (auto& e : evFrame) (void)hipEventDestroy( e );
-	for (auto& e : evStage) (void)hipEventDestroy( e );
-	for (hipEvent_t* e : { &evTlasReady, &evTlasFree[0], &evTlasFree[1] }) { if (*e) (void)hipEventDestroy( *e ); *e = nullptr; }
-	for (int i = 0; i < 2; i++) { if (stage[i]) (void)hipHostFree( stage[i] ); stage[i] = nullptr, stageBytes[i] = 0; }
 	if (glResource) (void)hipGraphicsUnregisterResource( glResource );
 	glResource = nullptr, glTexture = 0;
 	if (hostStats) (void)hipHostFree( hostStats );

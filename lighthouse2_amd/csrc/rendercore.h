@@ -4,75 +4,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
-#include <functional>
-#include <memory>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/lh2_core_types.h"
 #include "../../include/lh2_rendercore.h"
-#include "bvh_build.h"
-#include "bvh_gpu.h"
 #include "lh2_kernels.h"
 #include "lh2_filter.h"
 #include "lh2_device.h"
+#include "scene_accel.h"
 
 namespace lh2 {
-
-void FatalError( const char* fmt, ... );
-
-template <class T> struct DevBuf
-{
-	T* ptr = nullptr;
-	size_t count = 0;
-	DevBuf() = default;
-	DevBuf( const DevBuf& ) = delete;
-	DevBuf& operator=( const DevBuf& ) = delete;
-	~DevBuf() { free(); }
-	void free() { if (ptr) (void)hipFree( ptr ); ptr = nullptr; count = 0; }
-	void resize( size_t n )   /* discards contents */
-	{
-		if (n <= count && ptr) return;
-		free();
-		if (n == 0) n = 1;
-		if (hipMalloc( (void**)&ptr, n * sizeof( T ) ) != hipSuccess) FatalError( "hipMalloc of %zu bytes failed", n * sizeof( T ) );
-		count = n;
-	}
-	void adopt( T* p, size_t n ) { free(); ptr = p, count = n; }   /* takes ownership of a hipMalloc'ed block */
-	void upload( const T* src, size_t n, hipStream_t st )
-	{
-		resize( n );
-		if (n) if (hipMemcpyAsync( ptr, src, n * sizeof( T ), hipMemcpyHostToDevice, st ) != hipSuccess) FatalError( "upload failed" );
-	}
-};
-
-/* a deferred CPU BLAS build (RenderCore::FlushBuilds) and its host results.  Shared by the sub-cores of a MultiDevice:
-   the first core to flush runs it (once, std::call_once), every core uploads the results to its own device, and the last
-   reference frees them (round 6, VERDICT r5 #7: no N-fold build at deviceCount N) */
-struct HostBlas
-{
-	std::once_flag once;
-	std::function<void( HostBlas&, int )> job;   /* its argument: host threads for the build */
-	std::vector<float> nodes2, tris48, nodes4;
-	int leafTris = 0, nodeCount = 0, maxDepth = 0, depth4 = 0;
-	void Run( int threads );
-};
-
-struct CoreMeshHost   /* RenderCore always copies what it needs (rendercore.h:57): all of it on the device */
-{
-	int triCount = 0;
-	int leafTris = 0;                    /* triangle records of the BLAS leaves (> triCount with spatial splits) */
-	float aabbLo[3], aabbHi[3];          /* lo.x > hi.x: empty mesh */
-	DevBuf<float4> shadeTris;            /* CoreTri4[] in original order, for shading */
-	DevBuf<float4> bvhNodes, bvhTris;    /* BLAS with mesh-local refs; relocated into the scene arrays by UpdateToplevel */
-	int nodeCount = 0, maxDepth = 0;
-	DevBuf<float4> bvh4Nodes;            /* the same BLAS collapsed to BVH4 (CollapseBvh4), mesh-local refs */
-	int node4Count = 0, depth4 = 0;
-	std::shared_ptr<HostBlas> build;     /* a deferred CPU build not uploaded yet (null: none) */
-};
-
-struct CoreInstanceHost { int mesh; float T[16]; float inv[16]; };
 
 /* one set of path buffers: rays, path state and hits.  A launch reads one set and (a shade launch) writes another */
 struct PathSet
@@ -239,9 +181,9 @@ public:
 	void SetGeometry( int meshIdx, const float* vertexData, int vertexCount, int triangleCount, const lh2_CoreTri* triangles, const uint32_t* alphaFlags );
 	/* MultiDevice: the same mesh as SetGeometry, sharing src's deferred CPU BLAS build (built once, uploaded here too) */
 	void AdoptGeometry( int meshIdx, int triangleCount, const lh2_CoreTri* triangles, const RenderCore& src );
-	void FlushPendingBuilds() { FlushBuilds(); }
-	static int BlasBuildCount();         /* CPU BLAS builds run in this process (the build-once check) */
-	void SetInstance( int instanceIdx, int meshIdx, const float* matrix16 );
+	void FlushPendingBuilds() { accel.FlushBuilds(); }
+	static int BlasBuildCount() { return SceneAccel::BlasBuildCount(); }   /* CPU BLAS builds run in this process (the build-once check) */
+	void SetInstance( int instanceIdx, int meshIdx, const float* matrix16 ) { accel.SetInstance( instanceIdx, meshIdx, matrix16 ); }
 	void UpdateToplevel();
 	lh2_CoreStats GetCoreStats();
 
@@ -301,18 +243,12 @@ private:
 	FilterState fl;
 	/* the a-trous passes' tap source per pass (1: an LDS tile), by measurement (profiles/ *_ab_filter_lds.txt) */
 	static constexpr int kFilterLdsPick[3] = { 1, 1, 1 };
-	void ConcatenateBlas( int instanceCount );
-	void BuildBlas4( CoreMeshHost& m, const float* nodes2 );
-	void FlushBuilds();
-	bool pendingBuilds = false;
 #ifdef LH2_TOUCH
 	DevBuf<uint32_t> touchMap;           /* diagnostic build: the touched-record bitmap (lh2_trace4d.inc) */
 	uint32_t touchNodeWords = 0;
 	void TouchBegin();
 	void TouchReport( int pathLength );
 #endif
-	int buildThreads = 0;                /* host threads of the deferred BLAS builds (setting "buildThreads"; 0: LH2_BUILD_THREADS,
-	                                        OMP_NUM_THREADS or min(16, cores)) */
 	bool PathsFit( uint32_t paths ) const { return (size_t)paths + 64 <= ps.cap; }
 	void EnsurePaths( uint32_t paths );
 	void EnsureStack();
@@ -335,8 +271,7 @@ private:
 	TraceArgs UnitArgs( const float4* o, const float4* d, int n, uint32_t* cursor, int* gstack, uint4* hits ) const;
 	void CheckSceneError();
 	bool UsePackets() const;
-	SceneDev MakeSceneDev();             /* the latest TLAS slot's scene; the core stream waits for its update (SyncTlas) */
-	void SyncTlas();
+	SceneDev MakeSceneDev();             /* the latest TLAS slot's scene; the core stream waits for its update (SceneAccel::Fill) */
 	FrameSlots Slots() const;            /* of the frame parity PathStreams::fp */
 	int TraceGrid() const { return smCount * blocksPerCU; }
 	int UnitGrid() const { return smCount * std::min( blocksPerCU, unitTraceWaves == 8 ? traceBlocksPerCU8 : traceBlocksPerCU7 ); }
@@ -362,47 +297,7 @@ private:
 	}
 	int unitTraceWaves = 7;              /* the unit queries' variant: 7 (the config-2 bounce rays alone: 0.481 vs 0.515 ms, r04ag) */
 	bool initialized = false;
-	/* scene */
-	std::vector<CoreMeshHost*> meshes;
-	std::vector<CoreInstanceHost> instances;
-	bool geometryDirty = true, instancesDirty = true;
-	DevBuf<float4> dNodes, dTris;
-	DevBuf<float4> dNodes4;              /* BVH4: all BLAS (relocated), then the TLAS as two-child nodes */
-	DevBuf<uint4> dNodes4q;              /* the same nodes with quantized child boxes (GpuBvhBuilder::Quantize4) */
-	DevBuf<uint8_t> dInst[2];            /* DevInstance[], per TLAS slot */
-	DevBuf<lh2_CoreInstanceDesc> dInstDesc[2];
-	int tlasRoot = 0, blasNodeCount = 0, blasTriCount = 0, blasMeshTris = 0, sceneMaxDepth = 0;   /* blasTriCount: leaf triangle records; blasMeshTris: triangles */
-	std::vector<int> meshNodeBase, meshTriBase, meshNode4Base;
-	int tlasCapacity = 0, maxBlasDepth = 0;
-	int blasNode4Count = 0, maxBlas4Depth = 0;
-	int bvh4 = 1;                        /* build BVH4 copies of the BLAS (the default traversal loop needs them) */
-	/* the 8-wide compressed BVH of round 5 (W8, Ylitie et al. 2017) measured slower in every configuration (its node step
-	   issued 1.8x the BVH4 step's VALU for 0.72x the steps: profiles/r05_ab_w8.txt) and was removed in round 6 (commit
-	   22e0032 holds it) */
-	/* stack entries a ray may need: the BVH2 loop's BLAS depth, the BVH4 loop's 3 per level */
-	int StackDepthBound() const { return bvh4 ? std::max( maxBlasDepth, 3 * maxBlas4Depth ) : maxBlasDepth; }
-	bool tlasOnDevice = false;           /* TLAS of the last UpdateToplevel built by the GPU (depth in dTlasDepth) */
-	GpuBvhBuilder gpuBvh;
-	DevBuf<float> dMeshBounds;           /* 6 per mesh */
-	DevBuf<float> dInstT;                /* 16 per instance */
-	DevBuf<int> dInstMesh;
-	DevBuf<int> dSceneError, dTlasDepth; /* dSceneError: one flag per TLAS slot */
-	DevBuf<int> dBlasQError;             /* the BLAS quantizer's range flag (LH2_SCENE_ERR_QRANGE), copied into dSceneError per TLAS update */
-	uint8_t* stage[2] = {};              /* pinned staging of UpdateToplevel (double-buffered) */
-	size_t stageBytes[2] = {};
-	hipEvent_t evStage[2] = {};
-	int stageSlot = 0;
-	/* TLAS slots (round 4): an instance-only UpdateToplevel writes the instance tables, the TLAS (the BVH2 and BVH4 regions
-	   after the BLAS, tlasCapacity nodes per slot) and the scene-error flag of the slot no frame in flight reads, on the ahead
-	   stream behind the last frame that read that slot (evTlasFree), so an animated frame's primary launch can still run
-	   beside the previous frame; the core stream waits for the update (evTlasReady) before its next launch */
-	int tlasSlot = 0;
-	int tlasNodeCount[2] = { 1, 1 };     /* the nodes of each slot's TLAS (UpdateToplevel) */
-	bool tlasPending = false, tlasFreeValid[2] = {};
-	hipEvent_t evTlasReady = nullptr, evTlasFree[2] = {};
-	int TlasBase2( int s ) const { return blasNodeCount + s * tlasCapacity; }
-	int TlasBase4( int s ) const { return blasNode4Count + s * tlasCapacity; }
-	int* SceneErr( int s ) const { return dSceneError.ptr + s; }
+	SceneAccel accel;                    /* the scene: meshes, instances, BLAS, TLAS slots and their device arrays */
 	hipGraphicsResource_t glResource = nullptr;   /* registered GL_RGBA32F target texture */
 	uint32_t glTexture = 0;
 	DevBuf<uint4> dMaterials;
@@ -490,20 +385,7 @@ private:
 #else
 	static constexpr bool kCamAhead = LH2_CAM_AHEAD != 0;
 #endif
-	int bvhMaxLeaf = 1;
-	/* spatial splits (SBVH): overlap threshold x root area; 0 = off.  1e-3 (round 4; 1e-5 before): the same node steps and
-	   triangle tests per ray (tools/bvh_quality.cpp: config 2 26.62 / 6.78 vs 26.64 / 6.68, the room 14.58 / 1.83 both)
-	   at a third of the build time (config 2 0.39 vs 1.44 s, the room 1.26 vs 2.88 s; profiles/r04d_sbvh_alpha.txt) */
-	float bvhSpatial = 1e-3f;
-	float bvhSpatialBudget = 1.0f;       /* ... adding at most this many references per triangle */
-	/* ... in nodes of at least this many references (0: every node): 64 builds config 5's 100 meshes 17-20 % faster
-	   (setup 4.55 -> 3.64-3.76 s on one box) for 0.3 % more node steps (config-5 frame +0.4 %; config 2 and 3 within the
-	   noise), profiles/r04g_sbvh_build.txt, r04u_config5_setup.jsonl */
-	int bvhSpatialMinRefs = 64;
-	int bvh4Collapse = 1;                /* BVH4 collapse: 0 greedy (CollapseBvh4), 1 dynamic programming (CollapseBvh4Sah) */
 	float chordSplit = 0.35f;            /* extension rays with a chord through the scene box below this x its extent are traced last */
-	float sceneLo[3] = { 0, 0, 0 }, sceneHi[3] = { 0, 0, 0 };   /* world box of the instanced meshes (UpdateToplevel) */
-	float qBound = 0;                    /* |coordinate| bound of the world box and every mesh box, with slack (SceneDev::qBound) */
 	/* the path tail (k_trace_path4d): bounces pathTail .. maxPathLength traced and shaded in one launch,
 	   a wave shading its finished queries once pathTailBatch lanes hold one (or none walks); 0: a launch
 	   pair per bounce.  Config 3 (profiles/r02zb_ab_path_tail.txt): 2.542 -> 2.389 ms per frame at 3 / 56 */
@@ -538,7 +420,6 @@ private:
 	int TraceVersion() const;
 	int unitCoherent = 0;
 	int packetPrimary = -1;              /* wave-uniform packet traversal for 8x8-tiled primary rays (-1: by scene size) */
-	int gpuBuild = 0, gpuTlas = 1;       /* BLAS builder (1: GPU PLOC, 0: CPU binned SAH); TLAS on the GPU */
 	double frameHostMs = 0;
 	int samplesTaken = 0;
 	bool firstConvergingFrame = false;

@@ -173,7 +173,7 @@ def test_repeated_settings_each_frame():
 @pytest.mark.parametrize("devices", [2, 3])
 def test_blas_built_once_per_mesh(devices):
     """the in-core multi-device path builds each mesh's BLAS once on the host and uploads it to every
-    sub-core (RenderCore::AdoptGeometry shares core 0's deferred build), instead of one build per device.  The process's
+    sub-core (SceneAccel::AdoptGeometry shares core 0's deferred build), instead of one build per device.  The process's
     CPU build count ("blasBuilds") grows by the mesh count whatever deviceCount is, and the frame still equals the
     one-device frame."""
     w, h = 96, 54
@@ -196,3 +196,76 @@ def test_blas_built_once_per_mesh(devices):
     bn, an = builds_during(devices)
     assert b1 == len(sc.meshes) and bn == len(sc.meshes), (b1, bn)
     assert rel_l2(an[..., :3], a1[..., :3]) <= 1e-6
+
+
+# ---- the build-once cases ADVICE round 6 names as uncovered: a superseded pending build, a mesh set again after its
+# upload, and GPU builds under deviceCount 2.  Small shapes: 3 meshes of 500 random triangles, 64 x 40 ----
+_SMALL = dict(meshes=3, tris_per_mesh=500, width=64, height=40, grid=2, spacing=12.0)
+
+
+def _small_scene():
+    return scene.instanced_scene(**_SMALL)
+
+
+def _build_run(sc, devices, settings=(), first=None, reset=None):
+    """One frame of sc on a core of `devices` sub-cores.  first: mesh 0's geometry set before the scene's own (both before
+    update_toplevel); reset: mesh 0's geometry set again after a rendered frame, then update_toplevel and one more frame.
+    Returns the CPU BLAS builds of the load (and of the re-set step, when there is one) and the last accumulator."""
+    w, h = _SMALL["width"], _SMALL["height"]
+    c = RenderCore(device=0)
+    try:
+        if devices > 1:
+            c.setting("deviceCount", devices)
+        for k, v in settings:
+            c.setting(k, v)
+        b0 = c.get_setting("blasBuilds")
+        if first is not None:
+            c.set_geometry(0, first)
+        sc.load_into(c)
+        c.set_target(w, h, 1)
+        sc.render_frame(c, converge=1)
+        b1 = c.get_setting("blasBuilds")
+        if reset is not None:
+            c.set_geometry(0, reset)
+            c.update_toplevel()
+            sc.render_frame(c, converge=1)
+        return b1 - b0, c.get_setting("blasBuilds") - b1, c.accumulator()
+    finally:
+        c.close()
+
+
+def test_superseded_pending_build_is_not_run():
+    """Mesh 0 gets a first geometry and then its real one before the scene is first needed: the first deferred build is
+    dropped, not run (one build per mesh, with 1 device and with 2), and the frame is that of the final geometry."""
+    sc = _small_scene()
+    first = scene.random_triangles(_SMALL["tris_per_mesh"], seed=0x0badcafe)
+    _, _, ref = _build_run(sc, 1)
+    for devices in (1, 2):
+        builds, _, acc = _build_run(sc, devices, first=first)
+        print(f"{devices} device(s): {builds} builds, rel-L2 vs the one-device frame {rel_l2(acc[..., :3], ref[..., :3]):.2e}")
+        assert builds == len(sc.meshes), (devices, builds)
+        assert rel_l2(acc[..., :3], ref[..., :3]) <= 1e-6
+
+
+def test_geometry_set_again_after_upload_builds_once():
+    """A mesh set again after its BLAS was uploaded (core 0 holds no pending build of it any more until its own
+    SetGeometry): exactly one more build, with 1 device and with 2, and the same frame."""
+    sc = _small_scene()
+    again = scene.random_triangles(_SMALL["tris_per_mesh"], seed=0x0badcafe)
+    _, b1, a1 = _build_run(sc, 1, reset=again)
+    _, b2, a2 = _build_run(sc, 2, reset=again)
+    print(f"builds of the re-set step: {b1} (1 device), {b2} (2 devices); rel-L2 {rel_l2(a2[..., :3], a1[..., :3]):.2e}")
+    assert b1 == 1 and b2 == 1, (b1, b2)
+    assert rel_l2(a2[..., :3], a1[..., :3]) <= 1e-6
+
+
+def test_gpu_build_under_two_devices():
+    """gpuBuild 1: every sub-core builds its BLAS on its own device (nothing to share), no CPU build runs (500 random
+    triangles do not reach the deep-tree fallback), and the frame equals the one-device gpuBuild 1 frame."""
+    sc = _small_scene()
+    st = (("gpuBuild", 1),)
+    b1, _, a1 = _build_run(sc, 1, settings=st)
+    b2, _, a2 = _build_run(sc, 2, settings=st)
+    print(f"CPU builds: {b1} (1 device), {b2} (2 devices); rel-L2 {rel_l2(a2[..., :3], a1[..., :3]):.2e}")
+    assert b1 == 0 and b2 == 0, (b1, b2)
+    assert rel_l2(a2[..., :3], a1[..., :3]) <= 1e-6

@@ -590,7 +590,7 @@ def test_stale_tlas_region_is_not_quantized(gpu_tlas):
     """The TLAS slots hold tlasCapacity nodes; a TLAS update writes only the nodes its tree has.  The rest is an earlier,
     larger TLAS or memory never written, which may hold huge finite boxes.  Round 4's range check (k_quantize4) fired on
     such memory (`test_traversal_variants_bitexact[7-1-2]`, fixed by NaN-filling the region at allocation, 651cce0);
-    since round 5 the BVH4 copy and the quantizer touch only the TLAS's own nodes (rendercore.cpp UpdateToplevel).  Here
+    since round 5 the BVH4 copy and the quantizer touch only the TLAS's own nodes (scene_accel.cpp UpdateToplevel).  Here
     both slots are filled with 3e38 (finite: it passes k_quantize4's validity test and needs a grid exponent far past
     LH2_QEXP_MAX) before an instance update: the frame must render, equal to the same frames without the fill."""
     from lighthouse2_amd.core import RenderCore
