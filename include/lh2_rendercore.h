@@ -34,6 +34,7 @@
      lh2_core_trace_any, lh2_core_trace_closest_device, lh2_core_generate_eye_rays,
      lh2_core_scene_info, lh2_core_debug_shadow_rays, lh2_core_debug_bvh4, lh2_core_debug_poison_tlas, lh2_core_get_setting, lh2_set_device, lh2_xorshift_floats, lh2_version,
      lh2_core_filter_buffer, lh2_core_filter_times, lh2_core_filter_unit (the denoise mode, setting "filter"),
+     lh2_core_taa_times, lh2_core_taa_unit (its TAA stage, setting "TAA"),
      lh2_core_bsdf_unit (the shade kernels' BSDF on host records).
 */
 #ifndef LH2_RENDERCORE_H
@@ -116,8 +117,9 @@ enum
 	LH2_FILTER_BUF_MOMENTS,        /* float4 */
 	LH2_FILTER_BUF_SHADING,        /* prepare's output: direct + indirect, 5:11 fixed point */
 	LH2_FILTER_BUF_PHASE1, LH2_FILTER_BUF_PHASE2,   /* the same format */
-	LH2_FILTER_BUF_PHASE3,         /* the frame: linear radiance */
+	LH2_FILTER_BUF_PHASE3,         /* the last pass's output, linear radiance: the frame, or the TAA stage's input if the last frame ran it */
 	LH2_FILTER_BUF_PREVWORLDPOS, LH2_FILTER_BUF_PREVMOMENTS,
+	LH2_FILTER_BUF_TAA, LH2_FILTER_BUF_PREVTAA,   /* setting "TAA" only: the TAA pass's pixels (sqrt of radiance, w = 0) of the last frame and of the one before */
 	LH2_FILTER_BUF_COUNT
 };
 int lh2_core_filter_buffer( lh2_core core, int which, void* out );
@@ -138,6 +140,19 @@ typedef struct
 	const float* in; const float* prev; float* out;
 } lh2_FilterUnit;
 int lh2_core_filter_unit( lh2_core core, const lh2_FilterUnit* unit );
+/* the TAA stage (setting "TAA", applied while "filter" is): the last frame's TAA pass and unsharpen (ms), zeros if it ran
+   none; and one of its kernels on host arrays of any w x h, whatever the settings: stage 0 the TAA pass (reads in = linear
+   radiance, prev = the previous frame's TAA pixels, motion; writes out = this frame's TAA pixels), stage 1 the unsharpen
+   (reads in = TAA pixels; writes out = the frame).  in, prev, out: 4 floats per pixel; motion: 2 */
+int lh2_core_taa_times( lh2_core core, float* ms2 );
+typedef struct
+{
+	int stage, w, h;
+	int historyValid;              /* stage 0; 0: every pixel passes through */
+	int lds;                       /* stage 0: the 3 x 3 neighbourhood from an LDS tile (1) or through the caches (0) */
+	const float* in; const float* prev; const float* motion; float* out;
+} lh2_TaaUnit;
+int lh2_core_taa_unit( lh2_core core, const lh2_TaaUnit* unit );
 
 /* the Disney BSDF of the shade kernels (their EvaluateBSDF / SampleBSDF device functions) on n host records, against the
    materials of lh2_core_set_materials through the kernels' own unpacking of the uploaded records (untextured: the maps

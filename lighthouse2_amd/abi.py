@@ -85,6 +85,12 @@ class FilterUnit(C.Structure):
                 ("prevMoments", C.c_void_p), ("in_", C.c_void_p), ("prev", C.c_void_p), ("out", C.c_void_p)]
 
 
+class TaaUnit(C.Structure):
+    """lh2_TaaUnit (include/lh2_rendercore.h): one kernel of the TAA stage on host arrays."""
+    _fields_ = [("stage", C.c_int), ("w", C.c_int), ("h", C.c_int), ("historyValid", C.c_int), ("lds", C.c_int),
+                ("in_", C.c_void_p), ("prev", C.c_void_p), ("motion", C.c_void_p), ("out", C.c_void_p)]
+
+
 class BsdfUnit(C.Structure):
     """lh2_BsdfUnit (include/lh2_rendercore.h): EvaluateBSDF / SampleBSDF on host records (bsdf_records)."""
     _fields_ = [("sample", C.c_int), ("n", C.c_int), ("in_", C.c_void_p), ("out", C.c_void_p)]

@@ -86,6 +86,8 @@ def load_library(path: str | os.PathLike | None = None) -> C.CDLL:
         "lh2_core_filter_buffer": [_P, C.c_int, _P],
         "lh2_core_filter_times": [_P, _F],
         "lh2_core_filter_unit": [_P, C.POINTER(abi.FilterUnit)],
+        "lh2_core_taa_times": [_P, _F],
+        "lh2_core_taa_unit": [_P, C.POINTER(abi.TaaUnit)],
         "lh2_core_bsdf_unit": [_P, C.POINTER(abi.BsdfUnit)],
     }
     for name, args in sig.items():
@@ -327,6 +329,7 @@ class RenderCore:
         "deltaDepth": (3, np.float32, 4), "motion": (4, np.float32, 2), "moments": (5, np.float32, 4),
         "shading": (6, np.uint32, 4), "phase1": (7, np.uint32, 4), "phase2": (8, np.uint32, 4), "phase3": (9, np.float32, 4),
         "prevWorldPos": (10, np.float32, 4), "prevMoments": (11, np.float32, 4),
+        "taa": (12, np.float32, 4), "prevtaa": (13, np.float32, 4),     # setting "TAA" only
     }
 
     def filter_buffer(self, name: str) -> np.ndarray:
@@ -375,6 +378,29 @@ class RenderCore:
         if stage == 0:
             return dict(shading=out, motion=motion, moments=moments, features=features)
         return dict(out=out)
+
+    def taa_times(self) -> np.ndarray:
+        """Kernel times of the last frame's TAA stage in ms: the TAA pass and the unsharpen; zeros if it ran none."""
+        out = np.zeros(2, np.float32)
+        self._chk(self.lib.lh2_core_taa_times(self.h, _fp(out)))
+        return out
+
+    def taa_unit(self, stage: int, *, in_, prev=None, motion=None, history_valid: bool = True, lds: bool = True) -> np.ndarray:
+        """Run the TAA pass (stage 0: in_ = linear radiance, prev = the previous frame's TAA pixels, motion) or the
+        unsharpen (stage 1: in_ = TAA pixels) on host arrays of shape (h, w, 4) (motion: (h, w, 2)); returns (h, w, 4).
+        lds picks the TAA pass's tap source (an LDS tile, or L1 / L2); the unsharpen has one variant."""
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        in_, prev, motion = f32(in_), f32(prev), f32(motion)
+        h, w = in_.shape[:2]
+        if in_.shape != (h, w, 4) or (prev is not None and prev.shape != (h, w, 4)) or (motion is not None and motion.shape != (h, w, 2)):
+            raise ValueError("taa_unit: in_ and prev are (h, w, 4), motion is (h, w, 2)")
+        out = np.zeros((h, w, 4), np.float32)
+        u = abi.TaaUnit()
+        u.stage, u.w, u.h, u.historyValid, u.lds = int(stage), w, h, int(history_valid), int(lds)
+        u.in_, u.prev, u.motion, u.out = ptr(in_), ptr(prev), ptr(motion), ptr(out)
+        self._chk(self.lib.lh2_core_taa_unit(self.h, C.byref(u)))
+        return out
 
     def bsdf_unit(self, sample: bool, records) -> np.ndarray:
         """The shade kernels' EvaluateBSDF (sample False) or SampleBSDF on abi.bsdf_records, against the materials of

@@ -11,6 +11,10 @@
                         where the reference's vector carries the offset)
      k_filter_atrous    three edge-stopping a-trous passes (steps 1, 2, 4); the first also blends with the previous frame's
                         first-pass output, the last remodulates by albedo and writes the frame
+   and, with the setting "TAA" on as well (TAApassKernel / unsharpenTAAKernel; the last pass then writes `linear`):
+     k_filter_taa       temporal antialiasing in gamma space: the previous frame's TAA pixels at the motion vector
+                        (Mitchell-Netravali), clamped in YCoCg to this frame's 3 x 3 neighbourhood, blended 0.9 : 0.1
+     k_filter_unsharpen sharpens what TAA blurred, squares the gamma away and writes the frame
    Buffers (w x h records each):
      features  uint4   x: albedo 10:11:11; y: packed normal (PackNormal2) + specular bit; z: hit distance (float bits);
                        w: history count (bits 0-3), specular flag (bits 4-5), material id (from bit 6)
@@ -18,7 +22,9 @@
      deltaDepth float4 zw: depth change towards pixel (x + 1, y) and (x, y + 1) along the hit triangle's plane
      motion    float2  the pixel's position in the previous frame (+ 0.5)
      moments   float4  luminance and squared luminance of direct and indirect light, blended over time
-     shading and the pass outputs: float4 holding two rgb triples as 5:11 fixed point (filter_combine) */
+     shading and the pass outputs: float4 holding two rgb triples as 5:11 fixed point (filter_combine)
+     linear    float4  TAA only: the last pass's output (linear radiance, w = 1)
+     taa       float4  TAA only, a pair like the history pairs: sqrt of the antialiased radiance, at most 10, w = 0 */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,11 +62,24 @@ struct FilterAtrousArgs
 	int lds;                         /* taps from an LDS tile (1) or straight from memory through L1 / L2 (0) */
 };
 
+struct FilterTaaArgs   /* k_filter_taa and k_filter_unsharpen */
+{
+	const float4* in;                /* taa: the last pass's linear output; unsharpen: the taa pass's output */
+	const float4* prev;              /* taa: the previous frame's taa output */
+	const float2* motion;            /* taa */
+	float4* out;                     /* never `in` or `prev`: both kernels read their neighbours */
+	int w, h;
+	int historyValid;                /* taa; 0: the pixel passes through */
+	int lds;                         /* taa: the 3 x 3 neighbourhood from an LDS tile (1) or through L1 / L2 (0) */
+};
+
 extern "C" {
 /* the reprojection constants of a view (prepareFilter's host part) */
 void lh2_filter_view( const lh2_ViewPyramid* view, int h, float4 out[4] );
 void lh2_launch_filter_prepare( const FilterPrepareArgs* a, LaunchEvents ev, hipStream_t st );
 void lh2_launch_filter_atrous( const FilterAtrousArgs* a, LaunchEvents ev, hipStream_t st );
+void lh2_launch_filter_taa( const FilterTaaArgs* a, LaunchEvents ev, hipStream_t st );
+void lh2_launch_filter_unsharpen( const FilterTaaArgs* a, LaunchEvents ev, hipStream_t st );
 }
 
 /* ---- packed formats (tools_shared.h PackNormal2 / HDRtoRGB32 / CombineToFloat4 and their inverses) ---- */

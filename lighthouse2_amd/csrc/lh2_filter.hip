@@ -1,10 +1,13 @@
-/* lh2_filter.hip - the SVGF filter kernels (lh2_filter.h): k_filter_prepare and k_filter_atrous<PHASE, LDS>.
+/* lh2_filter.hip - the SVGF filter kernels (lh2_filter.h): k_filter_prepare, k_filter_atrous<PHASE, LDS>, and the
+   TAA stage k_filter_taa<LDS> / k_filter_unsharpen.
 
-   The arithmetic restates Lighthouse 2's prepareFilterKernel / applyFilterKernel (finalize_shared.h) with their
-   helpers (sampling_shared.h ReadTexelConsistent / ReadTexelConsistent2, tools_shared.h); the file is compiled like
-   the rest of the core (no FMA contraction), so tests/filter_ref.py restates it operation by operation.  Left out: the
-   TAA jitter (j0 = j1 = 0), TAApass / unsharpenTAA, and the sqrt round trip the reference needs only for TAA: the
-   last pass writes linear radiance.
+   The arithmetic restates Lighthouse 2's prepareFilterKernel / applyFilterKernel / TAApassKernel / unsharpenTAAKernel
+   (finalize_shared.h) with their helpers (sampling_shared.h ReadTexelConsistent / ReadTexelConsistent2 /
+   ReadTexelBmitchellNetravali, tools_shared.h); the file is compiled like the rest of the core (no FMA contraction),
+   so tests/filter_ref.py and tests/taa_ref.py restate it operation by operation.  Left out: the TAA jitter
+   (j0 = j1 = 0: DESIGN.md section 9).  The last pass writes linear radiance; the sqrt the reference's last pass takes
+   for TAA is taken by k_filter_taa on load.  Where the TAA stage departs from the reference's text (an output buffer of
+   its own, the bicubic footprint, the first frame, the frame's border): DESIGN.md section 9.
 
    The a-trous pass reads 21 taps of A and features (32 B each) per pixel; its unique traffic is 80 B per pixel.  A
    block filters a 32 x 8 tile; the LDS variant stages the tile with a halo of 2 x step pixels (36 x 12, 40 x 16,
@@ -363,6 +366,149 @@ __global__ __launch_bounds__( 256 ) void k_filter_atrous( const FilterAtrousArgs
 	else a.C[pixelIdx] = filter_combine( directFiltered, indirectFiltered );
 }
 
+/* ---- k_filter_taa / k_filter_unsharpen (setting "TAA") --------------------------------------- */
+/* both read a pixel's 3 x 3 neighbourhood.  The TAA pass converts each neighbour (sqrt, YCoCg): its LDS variant stages the
+   block's 32 x 8 tile with a halo of one pixel, converted once.  A thread stages its own pixel's cell, the block's first 84
+   threads one halo cell each as well; cells outside the frame are left out (never read).  The unsharpen reads its
+   neighbours as they are, through L1 / L2: a tile buys it nothing (profiles/ *_ab_taa_lds.txt) */
+#define TAA_TW (FILTER_TX + 2)
+#define TAA_TH (FILTER_TY + 2)
+LH2_DEV bool taa_halo_cell( const int t, int& tx, int& ty )
+{
+	if (t < TAA_TW) tx = t, ty = 0;
+	else if (t < 2 * TAA_TW) tx = t - TAA_TW, ty = TAA_TH - 1;
+	else if (t < 2 * TAA_TW + FILTER_TY) tx = 0, ty = t - 2 * TAA_TW + 1;
+	else if (t < 2 * TAA_TW + 2 * FILTER_TY) tx = TAA_TW - 1, ty = t - 2 * TAA_TW - FILTER_TY + 1;
+	else return false;
+	return true;
+}
+LH2_DEV float mitchell_netravali( const float v )   /* B = C = 1/3 */
+{
+	const float B = 1.0f / 3.0f, C = 1.0f / 3.0f, x = fabsf( v ), x2 = x * x, x3 = x2 * x;
+	if (x < 1) return (1.0f / 6.0f) * ((12 - 9 * B - 6 * C) * x3 + (-18 + 12 * B + 6 * C) * x2 + (6 - 2 * B));
+	if (x < 2) return (1.0f / 6.0f) * ((-B - 6 * C) * x3 + (6 * B + 30 * C) * x2 + (-12 * B - 48 * C) * x + (8 * B + 24 * C));
+	return 0.0f;
+}
+LH2_DEV v3 gamma3( const float4 c ) { return mk3( sqrtf( c.x ), sqrtf( c.y ), sqrtf( c.z ) ); }
+LH2_DEV float4 taa_cell( const float4 linear ) { const v3 c = rgb_to_ycocg( gamma3( linear ) ); return make_float4( c.x, c.y, c.z, 0.0f ); }
+
+/* temporal antialiasing of the filtered frame (TAApassKernel): in gamma space, the previous frame's result at the motion
+   vector (Mitchell-Netravali), clamped in YCoCg to this frame's 3 x 3 neighbourhood, 0.9 of it against 0.1 of the pixel.
+   Reads the last pass's linear output, writes gamma pixels to a buffer of its own (the next frame's history) */
+template <bool LDS>
+__global__ __launch_bounds__( 256 ) void k_filter_taa( const FilterTaaArgs a )
+{
+	const int w = a.w, h = a.h;
+	const int bx0 = (int)blockIdx.x * FILTER_TX, by0 = (int)blockIdx.y * FILTER_TY;
+	const int x = bx0 + (int)threadIdx.x, y = by0 + (int)threadIdx.y;
+	const bool inFrame = x < w && y < h;
+	const int pixelIdx = x + y * w;
+	const int lc = ((int)threadIdx.y + 1) * TAA_TW + (int)threadIdx.x + 1;   /* the pixel's tile cell */
+	__shared__ float4 sY[LDS ? TAA_TW * TAA_TH : 1];   /* the neighbourhood in YCoCg */
+	v3 g = s3( 0.0f ), newPixel = s3( 0.0f );
+	if (inFrame) g = gamma3( a.in[pixelIdx] ), newPixel = rgb_to_ycocg( g );
+	if (LDS)
+	{
+		if (inFrame) sY[lc] = make_float4( newPixel.x, newPixel.y, newPixel.z, 0.0f );
+		int tx, ty;
+		if (taa_halo_cell( (int)(threadIdx.y * FILTER_TX + threadIdx.x), tx, ty ))
+		{
+			const int gx = bx0 - 1 + tx, gy = by0 - 1 + ty;
+			if (gx >= 0 && gx < w && gy >= 0 && gy < h) sY[ty * TAA_TW + tx] = taa_cell( a.in[gx + gy * w] );
+		}
+		__syncthreads();
+	}
+	if (!inFrame) return;
+	v3 pixel = g;
+	const float2 m = a.motion[pixelIdx];
+	const float u = m.x - 0.5f, v = m.y - 0.5f;
+	if (a.historyValid && u >= 0 && u < (float)w && v >= 0 && v < (float)h)
+	{
+		/* the history: the kernel's support, floor( u ) - 1 .. floor( u ) + 2 per axis; taps outside the frame are skipped
+		   and the weights renormalised */
+		const int x1 = (int)floorf( u ) - 1, y1 = (int)floorf( v ) - 1;
+		float wx[4], wy[4];
+#pragma unroll
+		for (int i = 0; i < 4; i++) wx[i] = mitchell_netravali( (float)(x1 + i) - u ), wy[i] = mitchell_netravali( (float)(y1 + i) - v );
+		float totalWeight = 0;
+		v3 total = s3( 0.0f );
+#pragma unroll
+		for (int j = 0; j < 4; j++)
+		{
+			const int ty = y1 + j;
+			if (ty >= 0 && ty < h)
+			{
+#pragma unroll
+				for (int i = 0; i < 4; i++)
+				{
+					const int tx = x1 + i;
+					if (tx >= 0 && tx < w)
+					{
+						const float weight = wx[i] * wy[j];
+						total = add3( total, muls( xyz( a.prev[tx + ty * w] ), weight ) );
+						totalWeight += weight;
+					}
+				}
+			}
+		}
+		const v3 historyRgb = muls( total, 1.0f / totalWeight );
+		v3 history = rgb_to_ycocg( historyRgb );
+		/* the neighbours that take part (the reference's bounds: x > 1, y > 1 on the low side; / 9 whatever their number) */
+		v3 colorAvg = newPixel, colorVar = mul3( newPixel, newPixel );
+		auto tap = [&]( const int dx, const int dy ) {
+			const v3 f = LDS ? xyz( sY[lc + dy * TAA_TW + dx] ) : xyz( taa_cell( a.in[pixelIdx + dy * w + dx] ) );
+			colorAvg = add3( colorAvg, f ), colorVar = add3( colorVar, mul3( f, f ) );
+		};
+		if (x > 1)
+		{
+			if (y > 1) tap( -1, -1 );
+			tap( -1, 0 );
+			if (y < h - 1) tap( -1, 1 );
+		}
+		if (y > 1) tap( 0, -1 );
+		if (y < h - 1) tap( 0, 1 );
+		if (x < w - 1)
+		{
+			if (y > 1) tap( 1, -1 );
+			tap( 1, 0 );
+			if (y < h - 1) tap( 1, 1 );
+		}
+		const float k9 = 1.0f / 9.0f;
+		colorAvg = muls( colorAvg, k9 ), colorVar = muls( colorVar, k9 );
+		const v3 var = sub3( colorVar, mul3( colorAvg, colorAvg ) );
+		const v3 sigma = mk3( sqrtf( fmaxf( 0.0f, var.x ) ), sqrtf( fmaxf( 0.0f, var.y ) ), sqrtf( fmaxf( 0.0f, var.z ) ) );
+		history = clamp3( history, sub3( colorAvg, smul( 1.25f, sigma ) ), add3( colorAvg, smul( 1.25f, sigma ) ) );
+		pixel = ycocg_to_rgb( add3( muls( newPixel, 0.1f ), muls( history, 0.9f ) ) );
+		/* NaN: the pixel without its history.  The history's own sum is tested as well: rgb_to_ycocg's fminf( 4, . ) turns a NaN
+		   history into 4 before the blend's sum (the reference's only test) could show it */
+		const float s = pixel.x + pixel.y + pixel.z, hs = historyRgb.x + historyRgb.y + historyRgb.z;
+		if (s != s || hs != hs) pixel = ycocg_to_rgb( newPixel );
+	}
+	a.out[pixelIdx] = make_float4( fminf( 10.0f, pixel.x ), fminf( 10.0f, pixel.y ), fminf( 10.0f, pixel.z ), 0.0f );
+}
+
+/* what TAA blurred, sharpened again (unsharpenTAAKernel), and the gamma taken back: reads the TAA pass's pixels, writes the
+   frame (linear radiance, w = 1).  The frame's border pixels have no full neighbourhood: they are only squared */
+__global__ __launch_bounds__( 256 ) void k_filter_unsharpen( const FilterTaaArgs a )
+{
+	const int w = a.w, h = a.h;
+	const int x = (int)(threadIdx.x + blockIdx.x * FILTER_TX), y = (int)(threadIdx.y + blockIdx.y * FILTER_TY);
+	if (x >= w || y >= h) return;
+	const int pixelIdx = x + y * w;
+	v3 pixel = xyz( a.in[pixelIdx] );
+	if (x > 0 && y > 0 && x < w - 1 && y < h - 1)
+	{
+		auto tap = [&]( const int dx, const int dy ) { return xyz( a.in[pixelIdx + dy * w + dx] ); };
+		const v3 p0 = tap( -1, -1 ), p1 = tap( 0, -1 ), p2 = tap( 1, -1 ), p3 = tap( 1, 0 ), p4 = tap( 1, 1 ), p5 = tap( 0, 1 ), p6 = tap( -1, 1 ), p7 = tap( -1, 0 );
+		v3 sum = add3( smul( 0.35f, p0 ), smul( 0.5f, p1 ) );
+		sum = add3( sum, smul( 0.35f, p2 ) ), sum = add3( sum, smul( 0.5f, p3 ) ), sum = add3( sum, smul( 0.35f, p4 ) );
+		sum = add3( sum, smul( 0.5f, p5 ) ), sum = add3( sum, smul( 0.35f, p6 ) ), sum = add3( sum, smul( 0.5f, p7 ) );
+		const v3 sharp = sub3( muls( pixel, 2.7f ), smul( 0.5f, sum ) );
+		pixel = mk3( fmaxf( pixel.x, sharp.x ), fmaxf( pixel.y, sharp.y ), fmaxf( pixel.z, sharp.z ) );
+	}
+	a.out[pixelIdx] = make_float4( pixel.x * pixel.x, pixel.y * pixel.y, pixel.z * pixel.z, 1.0f );
+}
+
 /* ---- launchers -------------------------------------------------------------------------- */
 #define LH2_FLAUNCH( kernel, grid, block, st, ev, ... ) \
 	hipExtLaunchKernelGGL( kernel, grid, block, 0, st, (ev).start, (ev).stop, 0, __VA_ARGS__ )
@@ -401,5 +547,14 @@ void lh2_launch_filter_atrous( const FilterAtrousArgs* a, LaunchEvents ev, hipSt
 	case 7: LH2_FLAUNCH( (k_filter_atrous<3, true>), g, b, st, ev, *a ); break;
 	default: break;   /* the host passes phases 1 .. 3 only */
 	}
+}
+void lh2_launch_filter_taa( const FilterTaaArgs* a, LaunchEvents ev, hipStream_t st )
+{
+	const dim3 g = filter_grid( a->w, a->h ), b( FILTER_TX, FILTER_TY );
+	if (a->lds) LH2_FLAUNCH( k_filter_taa<true>, g, b, st, ev, *a ); else LH2_FLAUNCH( k_filter_taa<false>, g, b, st, ev, *a );
+}
+void lh2_launch_filter_unsharpen( const FilterTaaArgs* a, LaunchEvents ev, hipStream_t st )
+{
+	LH2_FLAUNCH( k_filter_unsharpen, filter_grid( a->w, a->h ), dim3( FILTER_TX, FILTER_TY ), st, ev, *a );
 }
 }

@@ -171,18 +171,39 @@ void RenderCore::EnsureFilterBuffers()
 {
 	const size_t n = (size_t)scrwidth * scrheight;
 	if (!fl.ev[0]) for (auto& e : fl.ev) CHK_HIP( hipEventCreate( &e ) );
-	if (fl.pixels == n || !n) return;
-	fl.features.resize( n ), fl.deltaDepth.resize( n ), fl.shading.resize( n ), fl.motion.resize( n );
-	for (int i = 0; i < 2; i++) fl.worldPos[i].resize( n ), fl.moments[i].resize( n ), fl.filtered[i].resize( n );
-	/* the history counts start at 0, and no record is read before it was written */
-	CHK_HIP( hipMemsetAsync( fl.features.ptr, 0, sizeof( uint4 ) * n, stream ) );
-	for (int i = 0; i < 2; i++)
+	if (!n) return;
+	if (fl.pixels != n)
 	{
-		CHK_HIP( hipMemsetAsync( fl.worldPos[i].ptr, 0, sizeof( float4 ) * n, stream ) );
-		CHK_HIP( hipMemsetAsync( fl.moments[i].ptr, 0, sizeof( float4 ) * n, stream ) );
-		CHK_HIP( hipMemsetAsync( fl.filtered[i].ptr, 0, sizeof( float4 ) * n, stream ) );
+		fl.features.resize( n ), fl.deltaDepth.resize( n ), fl.shading.resize( n ), fl.motion.resize( n );
+		for (int i = 0; i < 2; i++) fl.worldPos[i].resize( n ), fl.moments[i].resize( n ), fl.filtered[i].resize( n );
+		/* the history counts start at 0, and no record is read before it was written */
+		CHK_HIP( hipMemsetAsync( fl.features.ptr, 0, sizeof( uint4 ) * n, stream ) );
+		for (int i = 0; i < 2; i++)
+		{
+			CHK_HIP( hipMemsetAsync( fl.worldPos[i].ptr, 0, sizeof( float4 ) * n, stream ) );
+			CHK_HIP( hipMemsetAsync( fl.moments[i].ptr, 0, sizeof( float4 ) * n, stream ) );
+			CHK_HIP( hipMemsetAsync( fl.filtered[i].ptr, 0, sizeof( float4 ) * n, stream ) );
+		}
+		fl.pixels = n, fl.historyValid = false, fl.cur = 0;
 	}
-	fl.pixels = n, fl.historyValid = false, fl.cur = 0;
+	EnsureTaaBuffers();
+}
+
+/* the TAA stage's buffers (setting "TAA"), beside the filter's and of their size, only while both settings are applied;
+   new ones start without TAA history */
+void RenderCore::EnsureTaaBuffers()
+{
+	const size_t n = fl.pixels;
+	if (!TaaOn() || !n || fl.taaPixels == n) return;
+	fl.linear.resize( n ), fl.taa[0].resize( n ), fl.taa[1].resize( n );
+	CHK_HIP( hipMemsetAsync( fl.linear.ptr, 0, sizeof( float4 ) * n, stream ) );
+	for (int i = 0; i < 2; i++) CHK_HIP( hipMemsetAsync( fl.taa[i].ptr, 0, sizeof( float4 ) * n, stream ) );
+	fl.taaPixels = n, fl.taaValid = false;
+}
+void RenderCore::FreeTaaBuffers()
+{
+	fl.linear.free(), fl.taa[0].free(), fl.taa[1].free();
+	fl.taaPixels = 0, fl.taaValid = false;
 }
 
 /* the denoise mode allowed or not (MultiDevice): as if the setting "filter" changed */
@@ -297,6 +318,7 @@ void RenderCore::Setting( const char* name, float value )  /* rendercore.cpp:439
 				fl.features.free(), fl.deltaDepth.free(), fl.shading.free(), fl.motion.free();
 				for (int i = 0; i < 2; i++) fl.worldPos[i].free(), fl.moments[i].free(), fl.filtered[i].free();
 				fl.pixels = 0, fl.historyValid = false;
+				FreeTaaBuffers();
 			}
 			if (scrwidth)
 			{
@@ -312,7 +334,24 @@ void RenderCore::Setting( const char* name, float value )  /* rendercore.cpp:439
 	else if (!strcmp( name, "clampIndirect" )) clampIndirect = value;
 	/* the a-trous passes' taps: 1 from an LDS tile, 0 through L1 / L2, -1 the measured pick per pass (RunFilter) */
 	else if (!strcmp( name, "filterLds" )) filterLds = value < 0 ? -1 : value != 0;
-	/* other names ("TAA", ...) are ignored, as in the reference */
+	/* temporal antialiasing as the end of the filter chain (k_filter_taa, k_filter_unsharpen): applied only where the filter
+	   is (TaaOn); the wish is kept while it is not.  A RenderSystem host sends it before every frame */
+	else if (!strcmp( name, "TAA" ))
+	{
+		if ((value != 0) == taaOn) return;
+		const bool was = TaaOn();
+		taaOn = value != 0;
+		if (was != TaaOn() && initialized)
+		{
+			/* the frames in flight end; the stage's buffers come or go and it starts without history of its own.  The filter's
+			   history and the sample count stay */
+			CHK_HIP( hipStreamSynchronize( aheadStream ) );
+			CHK_HIP( hipStreamSynchronize( sideStream ) );
+			CHK_HIP( hipStreamSynchronize( stream ) );
+			if (was) FreeTaaBuffers(); else EnsureTaaBuffers();
+		}
+	}
+	/* other names are ignored, as in the reference */
 }
 
 /* the current value of a setting (extension: the reference has no getter); false for unknown names */
@@ -331,7 +370,8 @@ bool RenderCore::GetSetting( const char* name, float& value ) const
 		{ "terminalShade", (float)terminalShade }, { "traceBlocksPerCU", (float)ClosestBlocksPerCU( ScenePicksWaves() ) }, { "unitTraceWaves", (float)unitTraceWaves }, { "traceWaves", (float)traceWaves },
 		{ "unitCoherent", (float)unitCoherent }, { "traceVersion", (float)TraceVersion() },
 		{ "usePackets", (float)UsePackets() }, { "blasBuilds", (float)BlasBuildCount() },
-		{ "filter", (float)FilterOn() }, { "clampDirect", clampDirect }, { "clampIndirect", clampIndirect }, { "filterLds", (float)filterLds } };
+		{ "filter", (float)FilterOn() }, { "clampDirect", clampDirect }, { "clampIndirect", clampIndirect }, { "filterLds", (float)filterLds },
+		{ "TAA", (float)TaaOn() } };
 	for (const auto& e : t) if (!strcmp( name, e.n )) { value = e.v; return true; }
 	return false;
 }
@@ -586,6 +626,7 @@ FramePlan RenderCore::PlanFrame( const lh2_ViewPyramid& view, int converge ) con
 	   wavefront loop, one launch pair per bounce behind the previous frame - no path tail, no early or terminal shade, no
 	   overlap of consecutive frames; the accumulator (two planes) holds this frame's samples only, and the lens is a pinhole */
 	p.filt = FilterOn() && fl.pixels && p.tileRows == scrheight && !primeRef;
+	p.taa = p.filt && TaaOn() && fl.taaPixels;
 	p.aperture = p.filt ? 0.0f : view.aperture;
 	p.packets = tiledRays && UsePackets();
 	/* heavy-first primary packets: this frame reads the block the previous one recorded, and records into the
@@ -1024,7 +1065,7 @@ void RenderCore::FinishFrame( Frame& f )
 	{
 		/* the filter chain writes the frame; the finalize launch only delivers the statistics (no pixels).  The next frame stays
 		   behind this one */
-		RunFilter( f.view );
+		RunFilter( f.view, p.taa );
 		lh2_launch_finalize( accumulator.ptr, frame.ptr, 0, 1.0f, &fs, { nullptr, evFrame[1] }, stream, nullptr );
 		ps.relaid = true;
 	}
@@ -1034,7 +1075,7 @@ void RenderCore::FinishFrame( Frame& f )
 	if (glResource && !displayAtFinalize) CopyFrameToDisplay();
 	hostStats->rayCount[0] = ps.count;
 	ps.lastFused = p.pFrame, ps.lastSceneVersion = sceneVersion;
-	last = { f.pl, f.tailL, f.tailL ? p.maxPL : f.pl, p.early, f.sideOn, p.shadows, primeRef != 0, p.filt, p.pFrame && !p.serialize };
+	last = { f.pl, f.tailL, f.tailL ? p.maxPL : f.pl, p.early, f.sideOn, p.shadows, primeRef != 0, p.filt, p.pFrame && !p.serialize, p.taa };
 	statsPending = true;
 }
 
@@ -1050,8 +1091,9 @@ void RenderCore::CopyFrameToDisplay()
 
 
 /* the denoise chain of a frame (reference rendercore.cpp:827-862): prepare, three a-trous passes (the last one writes the
-   frame), then the buffers change roles for the next frame */
-void RenderCore::RunFilter( const lh2_ViewPyramid& view )
+   frame), then the buffers change roles for the next frame.  With taa (setting "TAA") the last pass writes fl.linear, the
+   TAA pass blends it into this frame's TAA pixels and the unsharpen writes the frame from those */
+void RenderCore::RunFilter( const lh2_ViewPyramid& view, bool taa )
 {
 	const int c = fl.cur, q = 1 - c;
 	CHK_HIP( hipEventRecord( fl.ev[0], stream ) );
@@ -1074,12 +1116,23 @@ void RenderCore::RunFilter( const lh2_ViewPyramid& view )
 	/* filtered[q] holds the previous frame's first pass: this frame's goes to filtered[c], the second pass then overwrites
 	   filtered[q], and the third writes the frame */
 	float4* const in[3] = { fl.shading.ptr, fl.filtered[c].ptr, fl.filtered[q].ptr };
-	float4* const out[3] = { fl.filtered[c].ptr, fl.filtered[q].ptr, frame.ptr };
+	float4* const out[3] = { fl.filtered[c].ptr, fl.filtered[q].ptr, taa ? fl.linear.ptr : frame.ptr };
 	for (int phase = 1; phase <= 3; phase++)
 	{
 		aa.phase = phase, aa.A = in[phase - 1], aa.B = phase == 1 ? fl.filtered[q].ptr : nullptr, aa.C = out[phase - 1];
 		aa.lds = filterLds >= 0 ? filterLds : kFilterLdsPick[phase - 1];
 		lh2_launch_filter_atrous( &aa, { nullptr, fl.ev[phase + 1] }, stream );
+	}
+	if (taa)
+	{
+		FilterTaaArgs ta{};
+		ta.in = fl.linear.ptr, ta.prev = fl.taa[q].ptr, ta.motion = fl.motion.ptr, ta.out = fl.taa[c].ptr;
+		ta.w = scrwidth, ta.h = scrheight, ta.historyValid = fl.historyValid && fl.taaValid;
+		ta.lds = filterLds >= 0 ? filterLds : kTaaLdsPick;
+		lh2_launch_filter_taa( &ta, { nullptr, fl.ev[5] }, stream );
+		ta.in = fl.taa[c].ptr, ta.prev = nullptr, ta.motion = nullptr, ta.out = frame.ptr;
+		lh2_launch_filter_unsharpen( &ta, { nullptr, fl.ev[6] }, stream );
+		fl.taaValid = true;
 	}
 	/* the next frame: worldPos, moments and the first pass's output become its history (the swaps of rendercore.cpp:856-862) */
 	fl.cur = q, fl.historyValid = true, fl.prevView = view;
@@ -1104,9 +1157,13 @@ void RenderCore::GetFilterBuffer( int which, void* out )
 	case LH2_FILTER_BUF_SHADING: src = fl.shading.ptr; break;
 	case LH2_FILTER_BUF_PHASE1: src = fl.filtered[c].ptr; break;
 	case LH2_FILTER_BUF_PHASE2: src = fl.filtered[q].ptr; break;
-	case LH2_FILTER_BUF_PHASE3: src = frame.ptr; break;
+	case LH2_FILTER_BUF_PHASE3: src = last.taa ? fl.linear.ptr : frame.ptr; break;
 	case LH2_FILTER_BUF_PREVWORLDPOS: src = fl.worldPos[q].ptr; break;
 	case LH2_FILTER_BUF_PREVMOMENTS: src = fl.moments[q].ptr; break;
+	case LH2_FILTER_BUF_TAA: case LH2_FILTER_BUF_PREVTAA:
+		if (!fl.taaPixels) FatalError( "the TAA stage is off (settings \"filter\" and \"TAA\"): it has no buffers" );
+		src = fl.taa[which == LH2_FILTER_BUF_TAA ? c : q].ptr;
+		break;
 	default: FatalError( "unknown filter buffer %d", which );
 	}
 	CHK_HIP( hipMemcpy( out, src, bytes, hipMemcpyDeviceToHost ) );
@@ -1115,6 +1172,33 @@ void RenderCore::GetFilterTimes( float* ms4 )
 {
 	Synchronize();
 	for (int k = 0; k < 4; k++) ms4[k] = last.filtered ? fl.ms[k] : 0.0f;
+}
+void RenderCore::GetTaaTimes( float* ms2 )
+{
+	Synchronize();
+	for (int k = 0; k < 2; k++) ms2[k] = last.filtered && last.taa ? fl.ms[4 + k] : 0.0f;
+}
+
+/* k_filter_taa (stage 0) or k_filter_unsharpen (stage 1) on host arrays (lh2_TaaUnit): upload, one launch, copy back.  The
+   core's own frame state is not touched */
+void RenderCore::TaaUnit( const lh2_TaaUnit& u )
+{
+	if (u.w < 1 || u.h < 1 || (uint64_t)u.w * u.h > (1u << 26) || u.stage < 0 || u.stage > 1) FatalError( "bad taa unit: stage %d, %d x %d", u.stage, u.w, u.h );
+	const size_t n = (size_t)u.w * u.h;
+	if (!u.in || !u.out || (u.stage == 0 && (!u.prev || !u.motion))) FatalError( "taa unit: null array" );
+	DevBuf<float4> in, prev, out; DevBuf<float2> motion;
+	in.upload( (const float4*)u.in, n, stream ), out.resize( n );
+	FilterTaaArgs ta{};
+	ta.in = in.ptr, ta.out = out.ptr, ta.w = u.w, ta.h = u.h, ta.historyValid = u.historyValid, ta.lds = u.lds;
+	if (u.stage == 0)
+	{
+		prev.upload( (const float4*)u.prev, n, stream ), motion.upload( (const float2*)u.motion, n, stream );
+		ta.prev = prev.ptr, ta.motion = motion.ptr;
+		lh2_launch_filter_taa( &ta, {}, stream );
+	}
+	else lh2_launch_filter_unsharpen( &ta, {}, stream );
+	CHK_HIP( hipMemcpyAsync( u.out, out.ptr, sizeof( float4 ) * n, hipMemcpyDeviceToHost, stream ) );
+	CHK_HIP( hipStreamSynchronize( stream ) );
 }
 
 /* one kernel of the chain on host arrays (lh2_FilterUnit): uploads what the stage reads, runs it, copies back what it writes */
@@ -1270,8 +1354,9 @@ void RenderCore::Synchronize()
 	coreStats.filterTime = 0;
 	if (last.filtered)
 	{
-		coreStats.filterTime = ms( fl.ev[0], fl.ev[4] );
-		for (int k = 0; k < 4; k++) fl.ms[k] = ms( fl.ev[k], fl.ev[k + 1] ) * 1e3f;
+		const int kernels = last.taa ? 6 : 4;
+		coreStats.filterTime = ms( fl.ev[0], fl.ev[kernels] );
+		for (int k = 0; k < 6; k++) fl.ms[k] = k < kernels ? ms( fl.ev[k], fl.ev[k + 1] ) * 1e3f : 0.0f;
 	}
 	for (int L = 1; L <= last.pathLengths && L <= 8; L++) lastKernelMs[L - 1] = trace( L ) * 1e3f;
 	coreStats.totalShadowRays = last.primeRef ? cn.totalShadowRays : QueuedShadowRays( cn );

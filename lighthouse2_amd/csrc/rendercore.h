@@ -102,6 +102,7 @@ struct PathStreams
 struct FramePlan
 {
 	bool restart, filt;                  /* the accumulation starts over; the denoise mode runs this frame */
+	bool taa;                            /* ... and ends in the TAA stage (setting "TAA") */
 	int tileRows;
 	uint32_t pathCount, segStride;
 	float aperture;
@@ -135,6 +136,7 @@ struct LastFrame
 	int pathLengths = 0;                 /* path lengths with a ray count (a path tail: all of them) */
 	bool early = false, sideOn = false;  /* its first shade launch ran early; its early shadow rays on the side stream */
 	bool shadows = true, primeRef = false, filtered = false, overlapped = false;
+	bool taa = false;                    /* a filtered frame that ended in the TAA stage */
 };
 
 struct Frame;   /* a frame being queued (rendercore.cpp) */
@@ -147,12 +149,17 @@ struct FilterState
 	DevBuf<float4> worldPos[2], moments[2], deltaDepth, shading;
 	DevBuf<float2> motion;
 	DevBuf<float4> filtered[2];          /* [cur]: the frame's phase-1 output (the next frame's history); [1 - cur]: phase 2's */
+	/* setting "TAA", allocated only while it and the filter are applied: the last pass's linear output, and the TAA pass's
+	   pixels ([cur]: this frame's, the next frame's history) */
+	DevBuf<float4> linear, taa[2];
+	size_t taaPixels = 0;                /* what they hold (0: not allocated) */
+	bool taaValid = false;               /* taa[1 - cur] holds the previous frame's pixels, if historyValid says there was one */
 	int cur = 0;
 	size_t pixels = 0;                   /* what the buffers hold (0: not allocated) */
 	bool historyValid = false;           /* the buffers of 1 - cur hold the previous frame */
 	lh2_ViewPyramid prevView{};
-	hipEvent_t ev[5] = {};               /* the chain's start, and the stop events of prepare and the three passes */
-	float ms[4] = {};                    /* the last filtered frame's kernel times (ms) */
+	hipEvent_t ev[7] = {};               /* the chain's start, and the stop events of prepare, the three passes, the TAA pass and the unsharpen */
+	float ms[6] = {};                    /* the last filtered frame's kernel times (ms); [4], [5]: the TAA stage's, 0 without it */
 };
 
 struct FrameStats   /* per-frame values delivered by k_finalize into pinned host memory */
@@ -203,9 +210,13 @@ public:
 	void GetFilterBuffer( int which, void* hostOut );
 	void GetFilterTimes( float* ms4 );
 	void FilterUnit( const lh2_FilterUnit& u );
+	/* the TAA stage (setting "TAA"): the last frame's two kernel times (zeros if it ran none), and its unit entry */
+	void GetTaaTimes( float* ms2 );
+	void TaaUnit( const lh2_TaaUnit& u );
 	void BsdfUnit( const lh2_BsdfUnit& u );
 	void SetFilterAllowed( bool on );    /* MultiDevice: a band has no neighbours across its edge, so no core of it filters */
 	bool FilterOn() const { return filterOn && filterAllowed; }
+	bool TaaOn() const { return taaOn && FilterOn(); }   /* applied only where the filter is */
 	/* in-process multi-device gather (multidevice.cpp): rows packed by the core of rank `rank` of a
 	   band partition, already on this device, into this accumulator (async); then the frame output
 	   of the whole accumulator again (finalizeRender + display copy, no statistics) */
@@ -236,13 +247,18 @@ public:
 private:
 	void EnsureBuffers();
 	void EnsureFilterBuffers();
-	void RunFilter( const lh2_ViewPyramid& view );
+	void RunFilter( const lh2_ViewPyramid& view, bool taa );
+	void EnsureTaaBuffers();
+	void FreeTaaBuffers();
 	bool filterOn = false, filterAllowed = true;
+	bool taaOn = false;                  /* the setting as sent; TaaOn(): applied */
 	int filterLds = -1;                  /* the a-trous passes' taps from an LDS tile (1), through L1 / L2 (0); -1: the measured pick per pass */
 	float clampDirect = LH2_FILTER_CLAMP_DIRECT, clampIndirect = LH2_FILTER_CLAMP_INDIRECT;
 	FilterState fl;
 	/* the a-trous passes' tap source per pass (1: an LDS tile), by measurement (profiles/ *_ab_filter_lds.txt) */
 	static constexpr int kFilterLdsPick[3] = { 1, 1, 1 };
+	/* the same for the TAA pass (profiles/ *_ab_taa_lds.txt; the unsharpen has one variant) */
+	static constexpr int kTaaLdsPick = 1;
 #ifdef LH2_TOUCH
 	DevBuf<uint32_t> touchMap;           /* diagnostic build: the touched-record bitmap (lh2_trace4d.inc) */
 	uint32_t touchNodeWords = 0;

@@ -1,14 +1,17 @@
-"""Times of the denoise mode (setting "filter") on one MI355X, and the filter-off regression against another build.
+"""Times of the denoise mode (settings "filter" and "TAA") on one MI355X, and the regression of the frame with the filter
+off, and with the filter on but TAA off, against another build.
 
   python tools/filter_time.py --out profiles/NAME_filter_time.json [--parent-tree DIR]
 
 Per configuration (config 2: 100k random triangles, primary + one bounce; config 3: the 1M-triangle room, maxPathLength 4;
-both 1920 x 1080, 1 spp): CoreStats::filterTime and the four kernels' times (HIP events: the launches' own stop events),
-means over --frames frames after --warmup, for the a-trous taps from the LDS tile, through L1 / L2, and the default
-pick; the frame time with the filter on and off; and the bytes-per-pixel floor of each kernel against 8 TB/s.
-With --parent-tree (a built checkout of the parent commit: its lighthouse2_amd package with the library) the filter-off
-frame times of this build and of that one are taken in fresh child processes, alternating, --repeats times each: the
-parent's own spread is the yardstick of the difference."""
+both 1920 x 1080, 1 spp): CoreStats::filterTime and the kernels' times (HIP events: the launches' own stop events), means
+over --frames frames after --warmup, for the taps (of the a-trous passes and the TAA pass) from the LDS tile, through
+L1 / L2, and the default pick, without TAA
+(four kernels) and with it (six: rows "taa_lds", "taa_l2", "taa_default"); the frame time with the filter off, on, and on
+with TAA; and the bytes-per-pixel floor of each kernel against 8 TB/s.
+With --parent-tree (a built checkout of the parent commit: its lighthouse2_amd package with the library) the frame times
+with the filter off, and with "filter" 1 and "TAA" left alone, of this build and of that one are taken in fresh child
+processes, alternating, --repeats times each: the parent's own spread is the yardstick of the difference."""
 from __future__ import annotations
 
 import argparse
@@ -35,6 +38,8 @@ FLOOR_BYTES = {
     "atrous1": 80 + 16 + 16 + 16 + 8,                           # + previous pass-1 output, worldPos, prevWorldPos, motion (8)
     "atrous2": 80,                                              # A, features, deltaDepth, moments in; C out
     "atrous3": 80,
+    "taa": 16 + 8 + 16 + 16,                                    # linear, motion (8), the history in; the TAA pixels out
+    "unsharpen": 16 + 16,                                       # the TAA pixels in; the frame out
 }
 PEAK = 8e12
 
@@ -55,17 +60,17 @@ def frame_ms(core, sc, frames, warmup):
     return (time.perf_counter() - t0) / frames * 1e3
 
 
-def filter_ms(core, sc, frames, warmup):
-    """Mean filterTime and kernel times (ms) over `frames` frames, each read after its frame."""
+def filter_ms(core, sc, frames, warmup, taa=False):
+    """Mean filterTime and kernel times (ms) over `frames` frames, each read after its frame; taa: the TAA stage's two as well."""
     for i in range(warmup):
         sc.render_frame(core, converge=1 if i == 0 else 0)
     rows, total = [], []
     for i in range(frames):
         sc.render_frame(core, converge=0)
         total.append(core.stats().filterTime * 1e3)
-        rows.append(core.filter_times())
+        rows.append(np.concatenate([core.filter_times(), core.taa_times()]) if taa else core.filter_times())
     k = np.mean(rows, 0)
-    return float(np.mean(total)), {n: float(v) for n, v in zip(("prepare", "atrous1", "atrous2", "atrous3"), k)}
+    return float(np.mean(total)), {n: float(v) for n, v in zip(("prepare", "atrous1", "atrous2", "atrous3", "taa", "unsharpen"), k)}
 
 
 def off_only(args):
@@ -77,6 +82,8 @@ def off_only(args):
         sc.load_into(c)
         c.set_target(W, H, 1)
         out[name] = round(frame_ms(c, sc, args.frames, args.warmup), 4)
+        c.setting("filter", 1)      # "TAA" as the build has it: off, or not known
+        out[name + "_filter_on"] = round(frame_ms(c, sc, args.frames, args.warmup), 4)
         c.close()
     print("FILTER_OFF " + json.dumps(out))
 
@@ -89,7 +96,7 @@ def main():
     ap.add_argument("--room-tris", type=int, default=1_000_000)
     ap.add_argument("--parent-tree", default="")
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--off-only", action="store_true", help="child mode: print the filter-off frame times of the build in --tree")
+    ap.add_argument("--off-only", action="store_true", help="child mode: print the frame times, filter off and on, of the build in --tree")
     ap.add_argument("--tree", default="")
     args = ap.parse_args()
     if args.off_only:
@@ -109,6 +116,12 @@ def main():
             total, kernels = filter_ms(c, sc, args.frames, args.warmup)
             r[label] = {"filterTime_ms": round(total, 4), "kernels_ms": {k: round(v, 4) for k, v in kernels.items()}}
         r["frame_ms_filter_on"] = round(frame_ms(c, sc, args.frames, args.warmup), 4)
+        c.setting("TAA", 1)
+        for label, lds in (("taa_lds", 1), ("taa_l2", 0), ("taa_default", -1)):
+            c.setting("filterLds", lds)
+            total, kernels = filter_ms(c, sc, args.frames, args.warmup, taa=True)
+            r[label] = {"filterTime_ms": round(total, 4), "kernels_ms": {k: round(v, 4) for k, v in kernels.items()}}
+        r["frame_ms_filter_taa_on"] = round(frame_ms(c, sc, args.frames, args.warmup), 4)
         c.close()
         rec[name] = r
         print(name, json.dumps(r), flush=True)
@@ -125,7 +138,7 @@ def main():
                 runs[label].append(json.loads(line[0][len("FILTER_OFF "):]))
                 print(label, runs[label][-1], flush=True)
         reg = {"parent_version": runs["parent"][0]["version"], "branch_version": runs["branch"][0]["version"]}
-        for cfg in ("config2", "config3"):
+        for cfg in ("config2", "config3", "config2_filter_on", "config3_filter_on"):
             pa, br = [r[cfg] for r in runs["parent"]], [r[cfg] for r in runs["branch"]]
             reg[cfg] = {"parent_ms": pa, "branch_ms": br, "parent_spread_ms": round(max(pa) - min(pa), 4),
                         "difference_of_means_ms": round(float(np.mean(br) - np.mean(pa)), 4)}
